@@ -9,12 +9,16 @@ loss = mse + vb, backward (RCCL gradient all-reduce through DDP when N > 1), Ada
 synthetic batch of BASELINE.md section 4 (no datasets / encoders exist offline).  Per-GPU batch is fixed, so
 scaling is weak; `value` = samples*steps per second summed over all ranks ("diffusion-steps/sec").
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 with the headline (metric, value,
+unit, higher_is_better, dtype, ms_per_step = wall time of one timed step) and the run's config.  `--dump-outputs DIR` also
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs()).  With `--full` the line also holds
   roofline     : the dominant C-ABI kernel of the timed region, timed with events on the launch stream
   kernels      : the same numbers for every C-ABI kernel
   gemm         : FLOPs and device time of the GEMMs of one step, as a fraction of the dense bf16 MFMA peak
   selective_scan_fn : the scan kernels on their own at the DiffMa-L/2 operator shape (north-star metric, N = 1 only)
   cpu_baseline : the oracle port of the same training step on the host cores (rank 0, N = 1 only)
+  comm         : the gradient all-reduce of a data-parallel run, from one profiled step after the timed region
+  configs      : short legs for the other BASELINE configurations (default model only)
 """
 import argparse
 import copy
@@ -60,7 +64,16 @@ def parse(argv=None):
     ap.add_argument("--legs", default="", help="comma list of the legs to run after the headline region (c2,c4,c5,c3_one_sample_graph); "
                                                "default: all four on one GPU, c3_one_sample_graph only on several")
     ap.add_argument("--leg-steps", type=int, default=10, help="timed steps of each leg")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the per-kernel roofline of the timed region, the comm block of a data-parallel "
+                         "run, the GEMM accounting, the scan micro-benchmark, the CPU baseline and the config legs (the options above "
+                         "that tune these act only with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss terms, sampled weights / samples) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 _T0 = time.perf_counter()
@@ -91,6 +104,35 @@ def update_ema(ema, model, decay=0.999):
     mp = list(model.parameters())
     torch._foreach_mul_(ep, decay)
     torch._foreach_add_(ep, mp, alpha=1 - decay)
+
+
+DUMP_SAMPLE = 1 << 21            # elements kept of a dumped output larger than this: 8 MB in float32, at most 16 MB per run
+
+
+def fixed_sample(tensors, k, seed):
+    """The tensors flattened and concatenated in order, or -- when they hold more than k elements -- about k of them: from each
+    tensor a share proportional to its size, at indices drawn from a fixed seed (the same for every run at the same shapes)."""
+    tensors = [t.detach() for t in tensors]
+    total = sum(t.numel() for t in tensors)
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for t in tensors:
+        flat = t.reshape(-1)
+        if total > k:
+            idx = torch.randint(0, flat.numel(), (min(flat.numel(), max(1, k * flat.numel() // total)),), generator=g)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float())
+    return torch.cat(parts)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+    _log(f"outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
 
 
 def _cpu_train_steps(model_name, timed, threads):
@@ -518,7 +560,7 @@ def main():
     if args.route_a:
         install_route_a()
     res = run_workload(args, dev, rank, world, force_ddp, headline=True)
-    legs = config_legs(args, dev, rank, world, force_ddp)
+    legs = config_legs(args, dev, rank, world, force_ddp) if args.full else None
     if rank == 0 and legs:
         res["configs"] = legs
         res["roofline"]["configs"] = legs       # the driver's record keeps `roofline` whole and only the NAMES of other extra keys
@@ -584,7 +626,8 @@ def config_legs(args, dev, rank, world, force_ddp):
 
 def run_workload(args, dev, rank, world, force_ddp, headline):
     """One workload: build the model, warm up, time `args.steps` steps (barrier + synchronize on both sides, max over ranks) and,
-    on rank 0, return the JSON record (None on the other ranks)."""
+    on rank 0, return the JSON record (None on the other ranks).  Everything after the timed steps other than the headline and
+    --dump-outputs runs only with --full."""
     import torch.distributed as dist
 
     from diffma_amd import hip_ops
@@ -602,6 +645,7 @@ def run_workload(args, dev, rank, world, force_ddp, headline):
     batch = synthetic_batch(B, tokens, dev, gen)
     kw = dict(y=batch["y"], y2=batch["y2"], w=batch["w"])
     amp = torch.bfloat16 if args.dtype == "bf16" else None
+    step_out = {}                                                # what the latest step computed besides its return value
 
     if args.mode == "train":
         ema = copy.deepcopy(model).requires_grad_(False)
@@ -631,7 +675,8 @@ def run_workload(args, dev, rank, world, force_ddp, headline):
             def step():
                 t = torch.randint(0, diffusion.num_timesteps, (B,), device=dev)
                 with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
-                    loss = diffusion.training_losses(net, batch["z"], t, kw)["loss"].mean()
+                    step_out["terms"] = diffusion.training_losses(net, batch["z"], t, kw)
+                    loss = step_out["terms"]["loss"].mean()
                 loss.backward()
                 opt.step()
                 update_ema(ema, model)
@@ -653,6 +698,7 @@ def run_workload(args, dev, rank, world, force_ddp, headline):
                 out = (sdiff.p_sample if args.sampler == "ddpm250" else sdiff.ddim_sample)(denoiser, state["x"], t, clip_denoised=False, model_kwargs=kw)
             state["x"] = out["sample"].float()
             state["i"] = state["i"] - 1 if state["i"] > 0 else sdiff.num_timesteps - 1
+            step_out["pred_xstart"] = out["pred_xstart"]
             return out["sample"]
 
     for _ in range(args.warmup):
@@ -670,7 +716,7 @@ def run_workload(args, dev, rank, world, force_ddp, headline):
             rows.sort(key=lambda e: -e.device_time_total)
             for e in rows[:40]:
                 f.write(f"{e.key:14s} n={e.count:4d} dev_us={e.device_time_total:10.1f}  {str(e.input_shapes)[:150]}\n")
-    timer = hip_ops.KernelTimer()
+    timer = hip_ops.KernelTimer() if args.full else None     # per-launch events over the timed region: the --full roofline
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -688,139 +734,153 @@ def run_workload(args, dev, rank, world, force_ddp, headline):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(last.detach().float()).all(), "non-finite loss/sample in the timed region"
+    if args.dump_outputs and headline and rank == 0:           # before any extra step of --full moves the weights
+        cap = lambda t: t if t.numel() <= DUMP_SAMPLE else fixed_sample([t], DUMP_SAMPLE, 0)
+        if args.mode == "train":
+            outs = {"loss": last}
+            outs.update({f"{k}_per_sample": cap(v) for k, v in step_out.get("terms", {}).items()})     # eager step: loss / mse / vb
+            outs["params"] = fixed_sample(model.parameters(), DUMP_SAMPLE, 0)           # the weights and the EMA after the step,
+            outs["ema_params"] = fixed_sample(ema.parameters(), DUMP_SAMPLE, 0)         # sampled at the same indices
+        else:
+            outs = {"sample": cap(last), "pred_xstart": cap(step_out["pred_xstart"])}
+        dump_outputs(args.dump_outputs, outs)
     comm = None
-    if (world > 1 or force_ddp) and args.mode == "train":
+    if args.full and (world > 1 or force_ddp) and args.mode == "train":
         comm = comm_accounting(step, model, net, args.graph, rank, world, os.environ.get("DIFFMA_GRAD_COMPRESSION", "none"),
                                gstep if (args.graph and args.mode == "train") else None)
 
-    if rank == 0:
+    if rank != 0:
+        return None
+    res = {
+        "metric": f"diffusion-steps/sec ({args.model}{' mamba2' if args.use_mamba2 else ''}, 224x224, {'training' if args.mode == 'train' else ('250-step DDPM sampling' if args.sampler == 'ddpm250' else '50-step DDIM sampling')}; samples*steps/s)",
+        "value": round(args.steps * B * world / elapsed, 3),
+        "unit": "samples*steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16 autocast (fp32 master weights, fp32 scan state)" if amp else "f32",
+        "data": "synthetic (BASELINE.md section 4), random-init weights with zero-init tensors re-randomised",
+        "config": {"workload": f"{args.model} DDP training step, 4x28x28 latents (196 tokens), batch {B}/GPU" + (", whole step replayed from a hipGraph" if (args.graph and world == 1 and not force_ddp) else (", step replayed from hipGraphs around the gradient all-reduce(s)" if args.graph else "")) if args.mode == "train"
+                   else f"{args.model} {'p_sample step (250-step respaced DDPM)' if args.sampler == 'ddpm250' else 'ddim_sample step (50-step DDIM)'}, batch {B}/GPU" + (", hipGraph replay" if args.graph else ""),
+                   "global_batch": B * world, "seq_len": tokens, "parallelism": f"dp{world}",
+                   "optimizer_steps_per_sec": round(args.steps / elapsed, 4), "gemm_tuning": args.gemm_tuning,
+                   **({"route": "A: three mamba_inner_fn calls per mixer, reference call pattern (block/mamba.py:346-348)"} if args.route_a else {})},
+    }
+    _log(f"timed region done: {1e3 * elapsed / args.steps:.1f} ms/step")
+    res["config"]["world_size_seen_by_rccl"] = dist.get_world_size() if dist.is_initialized() else 1
+    if not args.full:
+        return res
+
+    ksum = timer.summary()
+    kernel_source = "events on the launch stream over the timed region"
+    if args.mode == "sample" and args.graph:         # hipGraph replay: the denoiser's launches are not visible to the host-side timer
+        timer = hip_ops.KernelTimer()                 # (only the fused sampler kernel outside the graph was): time 2 eager steps instead
+        hip_ops.set_timer(timer)
+        for _ in range(2):
+            t_ = torch.full((B,), 5, device=dev, dtype=torch.long)
+            with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp is not None):
+                (sdiff.p_sample if args.sampler == "ddpm250" else sdiff.ddim_sample)(model.forward, state["x"], t_, clip_denoised=False, model_kwargs=kw)
+        torch.cuda.synchronize()
+        hip_ops.set_timer(None)
         ksum = timer.summary()
-        kernel_source = "events on the launch stream over the timed region"
-        if args.mode == "sample" and args.graph:         # hipGraph replay: the denoiser's launches are not visible to the host-side timer
-            timer = hip_ops.KernelTimer()                 # (only the fused sampler kernel outside the graph was): time 2 eager steps instead
-            hip_ops.set_timer(timer)
-            for _ in range(2):
-                t_ = torch.full((B,), 5, device=dev, dtype=torch.long)
-                with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp is not None):
-                    (sdiff.p_sample if args.sampler == "ddpm250" else sdiff.ddim_sample)(model.forward, state["x"], t_, clip_denoised=False, model_kwargs=kw)
-            torch.cuda.synchronize()
-            hip_ops.set_timer(None)
-            ksum = timer.summary()
-            kernel_source = "2 eager sampler steps after the timed region (the timed steps replay a hipGraph)"
-        elif not ksum:                                   # graphed training step: time the kernels of 2 eager steps instead
-            hip_ops.set_timer(timer)
-            for _ in range(2):
-                t_ = torch.randint(0, diffusion.num_timesteps, (B,), device=dev)
-                with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
-                    l_ = diffusion.training_losses(net, batch["z"], t_, kw)["loss"].mean()
-                l_.backward()
-                opt.zero_grad(set_to_none=True)
-            torch.cuda.synchronize()
-            hip_ops.set_timer(None)
-            ksum = timer.summary()
-            kernel_source = "2 eager forward+backward passes after the timed region (the timed steps replay a hipGraph)"
-        kernels = {}
-        for name, r in ksum.items():
-            # rate while at least one launch of the kernel is running (= bytes / avg_us when launches never overlap)
-            gbps = r["bytes_per_launch"] * r["launches"] / (r["busy_ms"] * 1e-3) / 1e9
-            gbps_d = r["design_bytes_per_launch"] * r["launches"] / (r["busy_ms"] * 1e-3) / 1e9
-            kernels[name] = dict(launches_per_step=r["launches"] / args.steps, avg_us=round(r["avg_us"], 2),
-                                 ms_per_step=round(r["total_ms"] / args.steps, 3), algorithmic_MB_per_launch=round(r["bytes_per_launch"] / 1e6, 3),
-                                 design_MB_per_launch=round(r["design_bytes_per_launch"] / 1e6, 3),
-                                 concurrent_launches=round(r["total_ms"] / r["busy_ms"], 3), GBps=round(gbps, 1),
-                                 frac_hbm_peak=round(gbps / HBM_PEAK_GBPS, 4), frac_design=round(gbps_d / HBM_PEAK_GBPS, 4))
-        nsteps_k = args.steps if "timed region" in kernel_source and "after" not in kernel_source else 2
-        for v in kernels.values():
-            v["launches_per_step"] = v["launches_per_step"] * args.steps / nsteps_k
-            v["ms_per_step"] = round(v["ms_per_step"] * args.steps / nsteps_k, 3)
-        dom = max(ksum, key=lambda n: ksum[n]["total_ms"])
-        r = ksum[dom]
-        per_launch = r["bytes_per_launch"] / (r["avg_us"] * 1e-6) / 1e9
-        conc = r["total_ms"] / r["busy_ms"]              # the block's two mixers run on two streams: launches of this kernel overlap
-        achieved = per_launch * conc                     # = all bytes of the kernel / time during which it was running
-        # HBM traffic of the same kernel at the same shape from the committed PMC passes (cannot be read live)
-        traffic = traffic_src = None
-        if args.model == "DiffMa-L/2" and not args.use_mamba2:
-            traffic, tsrc = load_profile_traffic(dom, args.dtype, 3 * B)
-            if traffic is not None:
-                traffic_src = f"{tsrc} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at this shape; not re-measured in this run)"
-        valu = load_profile_valu(dom, args.dtype) if (args.model == "DiffMa-L/2" and not args.use_mamba2) else None
-        design_per_launch = r["design_bytes_per_launch"] / (r["avg_us"] * 1e-6) / 1e9 * conc
-        mfma_roof = None
-        if r.get("flops_per_launch", 0) > 0:             # a matrix-pipe kernel dominates (dm_gemm at small batches): its roof is the MFMA peak
-            tf = r["flops_per_launch"] / (r["avg_us"] * 1e-6) / 1e12 * conc
-            mfma_roof = {"bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / MFMA_BF16_PEAK_TFLOPS, 4),
-                         "flops_per_launch": int(r["flops_per_launch"]),
-                         "note": "launch-bound regime: a few hundred workgroups of a 64 x 64 tile per launch, both mixers of a block in one launch"}
-        res = {
-            "metric": f"diffusion-steps/sec ({args.model}{' mamba2' if args.use_mamba2 else ''}, 224x224, {'training' if args.mode == 'train' else ('250-step DDPM sampling' if args.sampler == 'ddpm250' else '50-step DDIM sampling')}; samples*steps/s)",
-            "value": round(args.steps * B * world / elapsed, 3),
-            "unit": "samples*steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16 autocast (fp32 master weights, fp32 scan state)" if amp else "f32",
-            "data": "synthetic (BASELINE.md section 4), random-init weights with zero-init tensors re-randomised",
-            "config": {"workload": f"{args.model} DDP training step, 4x28x28 latents (196 tokens), batch {B}/GPU" + (", whole step replayed from a hipGraph" if (args.graph and world == 1 and not force_ddp) else (", step replayed from hipGraphs around the gradient all-reduce(s)" if args.graph else "")) if args.mode == "train"
-                       else f"{args.model} {'p_sample step (250-step respaced DDPM)' if args.sampler == 'ddpm250' else 'ddim_sample step (50-step DDIM)'}, batch {B}/GPU" + (", hipGraph replay" if args.graph else ""),
-                       "global_batch": B * world, "seq_len": tokens, "parallelism": f"dp{world}",
-                       "optimizer_steps_per_sec": round(args.steps / elapsed, 4), "gemm_tuning": args.gemm_tuning,
-                       **({"route": "A: three mamba_inner_fn calls per mixer, reference call pattern (block/mamba.py:346-348)"} if args.route_a else {})},
-            "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "frac_design": round(design_per_launch / HBM_PEAK_GBPS, 4),
-                         "design_bytes_per_launch": int(r["design_bytes_per_launch"]),
-                         "bytes_note": "algorithmic = SURVEY.md 8(d) for what the launch computes: the mixer's scans run WITHOUT z since round 3 "
-                                       "(gate hoisted into the merge), i.e. 5*s B per (seq, channel, step) element + fp32 dB/dC for the "
-                                       "backward and 3*s + B/C rows for the forward (7*s / 4*s with z: the stand-alone lines under "
-                                       "selective_scan_fn); design adds what this implementation moves on top (state checkpoints every 4 "
-                                       "steps, per-workgroup dB/dC partial rows, dA/dD/dbias partials)",
-                         "avg_us": round(r["avg_us"], 2), "algorithmic_bytes_per_launch": int(r["bytes_per_launch"]),
-                         "concurrent_launches": round(conc, 3), "achieved_per_launch": round(per_launch, 1),
-                         # the round-over-round yardstick: SURVEY.md 8(d)'s figure for the operator WITH z (7*s backward / 4*s forward per
-                         # element) over this launch's time -- the z / dz bytes themselves are moved by dm_token_merge / dm_gate_bwd now
-                         "frac_8d_with_z": (round((hip_ops.scan_bwd_algorithmic_bytes(3 * B, 1024, tokens, 16, 2, True) if dom.endswith("bwd")
-                                                   else hip_ops.scan_fwd_algorithmic_bytes(3 * B, 1024, tokens, 16, 2, 2, True))
-                                                  / (r["avg_us"] * 1e-6) / 1e9 * conc / HBM_PEAK_GBPS, 4)
-                                            if (dom.startswith("dm_selective_scan") and args.model.startswith("DiffMa-") and amp and not args.use_mamba2) else None),
-                         "limiter": "valu" if valu else "hbm",      # `bound` names the roof `peak` belongs to; the scans sit on the VALU pipe
-                         "valu": valu,
-                         "timing": kernel_source + "; achieved = algorithmic bytes per launch / avg_us x concurrent_launches "
-                                   "(concurrent_launches = sum of launch durations / union of launch intervals: 1.0 unless the "
-                                   "opt-in two-stream mode DIFFMA_OVERLAP_MIXERS=1 lets launches of the two mixers share the GPU)"},
-            "kernels": kernels,
-        }
-        if mfma_roof is not None:
-            res["roofline"].update(mfma_roof, limiter="launch / latency", hbm_view={k: res["roofline"][k] for k in ("achieved", "peak", "unit", "frac")})
-        _log(f"timed region done: {1e3 * elapsed / args.steps:.1f} ms/step")
-        res["config"]["world_size_seen_by_rccl"] = dist.get_world_size() if dist.is_initialized() else 1
-        if comm is not None:
-            res["comm"] = comm
-        if not args.no_extras:
-            if args.mode == "train" and world == 1 and not args.graph:      # extra steps on one rank only: never with peers waiting in an all-reduce
-                res["gemm"] = gemm_accounting(step, 1e3 * elapsed / args.steps)
-                _log("gemm accounting done")
-            if world == 1:
-                torch.cuda.empty_cache()
-                res["selective_scan_fn"] = scan_microbench(dev)
-                _log("scan micro-benchmark done")
-            # the north-star metric and the GEMM share ALSO inside `roofline` (the driver's record keeps that object and drops
-            # unknown top-level keys).  valu_ceiling_frac: the fraction of 8 TB/s the kernel's own instruction stream allows at 100 %
-            # VALU-pipe occupancy and the clock it runs at (counters in profiles/r0x_pmc_scan_kernels.txt)
-            ss = res.get("selective_scan_fn")
-            if ss:
-                pick = lambda d, ceil: {"us": d["us"], "frac": d["frac"], "valu_ceiling_frac": ceil}
-                res["roofline"]["selective_scan_fn"] = {
-                    "shape": ss["shape"], "target_frac": 0.70,
-                    "fp32_fwd": pick(ss["fp32"]["fwd"], 0.59), "bf16_fwd": pick(ss["bf16"]["fwd"], 0.30),
-                    "fp32_bwd": pick(ss["fp32"]["bwd_incl_partial_sums"], None), "bf16_bwd": pick(ss["bf16"]["bwd_incl_partial_sums"], 0.19)}
-            if res.get("gemm"):
-                res["roofline"]["gemm_frac_mfma_peak"] = res["gemm"]["frac_mfma_peak"]
-                res["roofline"]["gemm_ms_per_step"] = res["gemm"]["ms_per_step"]
-                res["roofline"]["gemm_own_kernels_ms_per_step"] = res["gemm"]["own_kernels"]["ms_per_step"]
-        if world == 1 and args.cpu_steps > 0 and args.mode == "train":
-            res["cpu_baseline"] = cpu_baseline(args, tokens)
-    return res if rank == 0 else None
+        kernel_source = "2 eager sampler steps after the timed region (the timed steps replay a hipGraph)"
+    elif not ksum:                                   # graphed training step: time the kernels of 2 eager steps instead
+        hip_ops.set_timer(timer)
+        for _ in range(2):
+            t_ = torch.randint(0, diffusion.num_timesteps, (B,), device=dev)
+            with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
+                l_ = diffusion.training_losses(net, batch["z"], t_, kw)["loss"].mean()
+            l_.backward()
+            opt.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        hip_ops.set_timer(None)
+        ksum = timer.summary()
+        kernel_source = "2 eager forward+backward passes after the timed region (the timed steps replay a hipGraph)"
+    kernels = {}
+    for name, r in ksum.items():
+        # rate while at least one launch of the kernel is running (= bytes / avg_us when launches never overlap)
+        gbps = r["bytes_per_launch"] * r["launches"] / (r["busy_ms"] * 1e-3) / 1e9
+        gbps_d = r["design_bytes_per_launch"] * r["launches"] / (r["busy_ms"] * 1e-3) / 1e9
+        kernels[name] = dict(launches_per_step=r["launches"] / args.steps, avg_us=round(r["avg_us"], 2),
+                             ms_per_step=round(r["total_ms"] / args.steps, 3), algorithmic_MB_per_launch=round(r["bytes_per_launch"] / 1e6, 3),
+                             design_MB_per_launch=round(r["design_bytes_per_launch"] / 1e6, 3),
+                             concurrent_launches=round(r["total_ms"] / r["busy_ms"], 3), GBps=round(gbps, 1),
+                             frac_hbm_peak=round(gbps / HBM_PEAK_GBPS, 4), frac_design=round(gbps_d / HBM_PEAK_GBPS, 4))
+    nsteps_k = args.steps if "timed region" in kernel_source and "after" not in kernel_source else 2
+    for v in kernels.values():
+        v["launches_per_step"] = v["launches_per_step"] * args.steps / nsteps_k
+        v["ms_per_step"] = round(v["ms_per_step"] * args.steps / nsteps_k, 3)
+    dom = max(ksum, key=lambda n: ksum[n]["total_ms"])
+    r = ksum[dom]
+    per_launch = r["bytes_per_launch"] / (r["avg_us"] * 1e-6) / 1e9
+    conc = r["total_ms"] / r["busy_ms"]              # the block's two mixers run on two streams: launches of this kernel overlap
+    achieved = per_launch * conc                     # = all bytes of the kernel / time during which it was running
+    # HBM traffic of the same kernel at the same shape from the committed PMC passes (cannot be read live)
+    traffic = traffic_src = None
+    if args.model == "DiffMa-L/2" and not args.use_mamba2:
+        traffic, tsrc = load_profile_traffic(dom, args.dtype, 3 * B)
+        if traffic is not None:
+            traffic_src = f"{tsrc} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at this shape; not re-measured in this run)"
+    valu = load_profile_valu(dom, args.dtype) if (args.model == "DiffMa-L/2" and not args.use_mamba2) else None
+    design_per_launch = r["design_bytes_per_launch"] / (r["avg_us"] * 1e-6) / 1e9 * conc
+    mfma_roof = None
+    if r.get("flops_per_launch", 0) > 0:             # a matrix-pipe kernel dominates (dm_gemm at small batches): its roof is the MFMA peak
+        tf = r["flops_per_launch"] / (r["avg_us"] * 1e-6) / 1e12 * conc
+        mfma_roof = {"bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / MFMA_BF16_PEAK_TFLOPS, 4),
+                     "flops_per_launch": int(r["flops_per_launch"]),
+                     "note": "launch-bound regime: a few hundred workgroups of a 64 x 64 tile per launch, both mixers of a block in one launch"}
+    res["roofline"] = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                      "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                      "frac_design": round(design_per_launch / HBM_PEAK_GBPS, 4),
+                      "design_bytes_per_launch": int(r["design_bytes_per_launch"]),
+                      "bytes_note": "algorithmic = SURVEY.md 8(d) for what the launch computes: the mixer's scans run WITHOUT z since round 3 "
+                                    "(gate hoisted into the merge), i.e. 5*s B per (seq, channel, step) element + fp32 dB/dC for the "
+                                    "backward and 3*s + B/C rows for the forward (7*s / 4*s with z: the stand-alone lines under "
+                                    "selective_scan_fn); design adds what this implementation moves on top (state checkpoints every 4 "
+                                    "steps, per-workgroup dB/dC partial rows, dA/dD/dbias partials)",
+                      "avg_us": round(r["avg_us"], 2), "algorithmic_bytes_per_launch": int(r["bytes_per_launch"]),
+                      "concurrent_launches": round(conc, 3), "achieved_per_launch": round(per_launch, 1),
+                      # the round-over-round yardstick: SURVEY.md 8(d)'s figure for the operator WITH z (7*s backward / 4*s forward per
+                      # element) over this launch's time -- the z / dz bytes themselves are moved by dm_token_merge / dm_gate_bwd now
+                      "frac_8d_with_z": (round((hip_ops.scan_bwd_algorithmic_bytes(3 * B, 1024, tokens, 16, 2, True) if dom.endswith("bwd")
+                                                else hip_ops.scan_fwd_algorithmic_bytes(3 * B, 1024, tokens, 16, 2, 2, True))
+                                               / (r["avg_us"] * 1e-6) / 1e9 * conc / HBM_PEAK_GBPS, 4)
+                                         if (dom.startswith("dm_selective_scan") and args.model.startswith("DiffMa-") and amp and not args.use_mamba2) else None),
+                      "limiter": "valu" if valu else "hbm",      # `bound` names the roof `peak` belongs to; the scans sit on the VALU pipe
+                      "valu": valu,
+                      "timing": kernel_source + "; achieved = algorithmic bytes per launch / avg_us x concurrent_launches "
+                                "(concurrent_launches = sum of launch durations / union of launch intervals: 1.0 unless the "
+                                "opt-in two-stream mode DIFFMA_OVERLAP_MIXERS=1 lets launches of the two mixers share the GPU)"}
+    res["kernels"] = kernels
+    if mfma_roof is not None:
+        res["roofline"].update(mfma_roof, limiter="launch / latency", hbm_view={k: res["roofline"][k] for k in ("achieved", "peak", "unit", "frac")})
+    if comm is not None:
+        res["comm"] = comm
+    if not args.no_extras:
+        if args.mode == "train" and world == 1 and not args.graph:      # extra steps on one rank only: never with peers waiting in an all-reduce
+            res["gemm"] = gemm_accounting(step, 1e3 * elapsed / args.steps)
+            _log("gemm accounting done")
+        if world == 1:
+            torch.cuda.empty_cache()
+            res["selective_scan_fn"] = scan_microbench(dev)
+            _log("scan micro-benchmark done")
+        # the north-star metric and the GEMM share ALSO inside `roofline` (the driver's record keeps that object and drops
+        # unknown top-level keys).  valu_ceiling_frac: the fraction of 8 TB/s the kernel's own instruction stream allows at 100 %
+        # VALU-pipe occupancy and the clock it runs at (counters in profiles/r0x_pmc_scan_kernels.txt)
+        ss = res.get("selective_scan_fn")
+        if ss:
+            pick = lambda d, ceil: {"us": d["us"], "frac": d["frac"], "valu_ceiling_frac": ceil}
+            res["roofline"]["selective_scan_fn"] = {
+                "shape": ss["shape"], "target_frac": 0.70,
+                "fp32_fwd": pick(ss["fp32"]["fwd"], 0.59), "bf16_fwd": pick(ss["bf16"]["fwd"], 0.30),
+                "fp32_bwd": pick(ss["fp32"]["bwd_incl_partial_sums"], None), "bf16_bwd": pick(ss["bf16"]["bwd_incl_partial_sums"], 0.19)}
+        if res.get("gemm"):
+            res["roofline"]["gemm_frac_mfma_peak"] = res["gemm"]["frac_mfma_peak"]
+            res["roofline"]["gemm_ms_per_step"] = res["gemm"]["ms_per_step"]
+            res["roofline"]["gemm_own_kernels_ms_per_step"] = res["gemm"]["own_kernels"]["ms_per_step"]
+    if world == 1 and args.cpu_steps > 0 and args.mode == "train":
+        res["cpu_baseline"] = cpu_baseline(args, tokens)
+    return res
 
 
 def finish(res, rank, world, force_ddp):

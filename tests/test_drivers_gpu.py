@@ -349,7 +349,7 @@ def test_bench_under_torchrun_over_rccl_one_rank(gpu, compression, tmp_path):
     env = dict(os.environ, BENCH_FORCE_DDP="1", DIFFMA_GRAD_COMPRESSION="none" if graph else compression, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "4",
-           "--cpu-steps", "0", "--no-extras"] + (["--graph"] if graph else [])
+           "--full", "--cpu-steps", "0", "--no-extras"] + (["--graph"] if graph else [])
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -369,6 +369,40 @@ def test_bench_under_torchrun_over_rccl_one_rank(gpu, compression, tmp_path):
         assert leg["comm"]["collectives_per_step"] == 1 and d["roofline"]["configs"]["c3_one_sample_graph"]["ms_per_step"] == leg["ms_per_step"]
     else:
         assert "configs" not in d
+
+
+@pytest.mark.parametrize("mode", ["train", "sample"])
+def test_bench_plain_run_dumps_its_last_step(gpu, mode, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the headline and none of the --full blocks;
+    with --dump-outputs DIR the arrays of the last timed step as finite float32 .npy files, 64 MB at most in all."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    B = 4 if mode == "train" else 2
+    shape = ["--batch-per-gpu", str(B)] + ([] if mode == "train" else ["--mode", "sample", "--model", "DiffMa-B/4", "--graph"])
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)] + shape
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_FORCE_DDP")}
+    out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["unit"] == "samples*steps/s"
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(1e3 * B / d["ms_per_step"], rel=1e-2)
+    assert not {"roofline", "kernels", "gemm", "selective_scan_fn", "cpu_baseline", "comm", "configs"} & set(d)
+    got = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir) if f.endswith(".npy")}
+    want = {"loss", "loss_per_sample", "mse_per_sample", "params", "ema_params"} if mode == "train" else {"sample", "pred_xstart"}
+    assert want <= set(got), sorted(got)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    if mode == "train":
+        assert got["loss_per_sample"].shape == (B,) and got["params"].shape == got["ema_params"].shape
+        np.testing.assert_allclose(got["loss"], got["loss_per_sample"].mean(), rtol=1e-3)
+    else:
+        assert got["sample"].shape == got["pred_xstart"].shape == (B, 4, 28, 28)
 
 
 def test_graphed_train_step_two_graphs_equal_one_graph(gpu, monkeypatch):

@@ -626,3 +626,20 @@ def test_bench_leg_specs_cover_the_baseline_configs():
         for k in spec:
             assert k == "what" or hasattr(a, k), (name, k)            # every override names a real bench argument
     assert bench.LEG_SPECS["c4"]["use_mamba2"] and bench.LEG_SPECS["c5"]["sampler"] == "ddim50" and bench.LEG_SPECS["c2"]["model"] == "DiffMa-B/4"
+
+
+def test_bench_plain_run_options_and_output_sample():
+    """A plain bench run measures the headline only (--full is off by default) and --steps is the number of timed steps; the
+    --dump-outputs sample of a large output holds at most the asked number of elements, at the same indices in every run."""
+    import bench
+
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs == ""
+    assert bench.parse(["--steps", "7", "--full"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    ps = [torch.randn(300, 1000), torch.randn(7, dtype=torch.bfloat16), torch.randn(5000)]
+    s = bench.fixed_sample(ps, 10000, 0)
+    assert s.dtype == torch.float32 and 0 < s.numel() <= 10000
+    assert torch.equal(s, bench.fixed_sample([p.clone() for p in ps], 10000, 0))
+    assert torch.equal(bench.fixed_sample(ps, 10 ** 6, 0), torch.cat([p.reshape(-1).float() for p in ps]))     # small enough: all of it
