@@ -898,6 +898,15 @@ def _ln_rows_per_block(Bsz, L):
     return LN_ROWS_PER_BLOCK
 
 
+LN_MAX_C = 1024          # 64 lanes x 16 values: the widest row dm_ln_mod_* / dm_blend_* take (pick_shape in csrc/block_ops.hip)
+
+
+def ln_mod_supported(C):
+    """Whether K8 (dm_ln_mod_fwd/bwd, dm_blend_fwd/bwd) takes rows of C values.  Every width from 1 to LN_MAX_C has an
+    instantiation (16-byte or scalar); wider rows are refused with DM_ERR_ARG, so the caller takes its eager formulation."""
+    return 1 <= int(C) <= LN_MAX_C
+
+
 def _ln_args(x, x2, gamma, beta, shift, scale, mask, eps, y_dtype):
     Bsz, L, C1 = x.shape
     C2 = x2.shape[-1] if x2 is not None else 0

@@ -196,7 +196,8 @@ class Spiral_MambaBlock(nn.Module):
             shift, scale, gate = linear_splitk(_silu_once(c, act), ada[1].weight, ada[1].bias).chunk(3, dim=1)
         else:
             shift, scale, gate = self.adaLN_modulation(c).chunk(3, dim=1)
-        if self.fused_elementwise and x.is_cuda:
+        # K8 normalises rows of D (LN / modulate / mask, blend) and of 2D (LN of cat[x_ssm, w_ssm]): wider blocks take the eager form
+        if self.fused_elementwise and x.is_cuda and hip_ops.ln_mod_supported(2 * x.shape[-1]):
             act = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
             block_ops.set_output_dtype(act)
             pt = block_ops.PASSTHROUGH and torch.is_grad_enabled()

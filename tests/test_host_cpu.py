@@ -192,6 +192,16 @@ def test_checkpoint_resume_and_sampler_load(tmp_path):
     mp.spawn(_resume_worker, args=(1, _free_port(), str(tmp_path)), nprocs=1, join=True)
 
 
+def test_ln_mod_supported_matches_the_k8_width_cap():
+    """K8 takes rows of 1 .. 1024 values (64 lanes x 16); Spiral_MambaBlock asks for 2 * D_dim (the LN of cat[x_ssm, w_ssm]), so
+    D_dim = 512 is fused and D_dim = 640 takes the eager formulation."""
+    from diffma_amd.hip_ops import LN_MAX_C, ln_mod_supported
+
+    assert LN_MAX_C == 1024
+    assert ln_mod_supported(1) and ln_mod_supported(198) and ln_mod_supported(1024)
+    assert not ln_mod_supported(0) and not ln_mod_supported(1025) and not ln_mod_supported(2 * 640)
+
+
 def test_kernel_timer_union_of_launch_intervals():
     """bench.py's roofline accounting: overlapping launches of one kernel (two-stream mode) count once in the busy time."""
     from diffma_amd.hip_ops import union_length

@@ -360,6 +360,54 @@ def test_block_fused_elementwise_matches_eager(gpu, amp, hidden, n):
     blk.fused_elementwise = True
 
 
+@pytest.mark.parametrize("amp", [None, torch.bfloat16])
+def test_block_wider_than_k8_takes_eager_form(gpu, amp):
+    """D_dim = 640: LN(cat[x_ssm, w_ssm]) normalises rows of 1280 values, more than K8 (csrc/block_ops.hip) takes.  The block
+    must run forward and backward (hip_ops.ln_mod_supported sends it to the eager formulation) and match fused_elementwise=False
+    within the bounds of test_block_fused_elementwise_matches_eager."""
+    from diffma_amd import hip_ops
+    from diffma_amd.mamba_block import Spiral_MambaBlock
+    from diffma_amd.tools import spiral
+
+    hidden, n, B = 640, 4, 2
+    assert hip_ops.ln_mod_supported(hidden) and not hip_ops.ln_mod_supported(2 * hidden)
+    torch.manual_seed(0)
+    orders, inverses = spiral(n)
+    blk = Spiral_MambaBlock(D_dim=hidden, E_dim=2 * hidden, dt_rank=16, dim_inner=2 * hidden, d_state=16, token_list=orders[0],
+                            token_list_reversal=orders[1], origina_list=inverses[0], origina_list_reversal=inverses[1]).to(gpu)
+    with torch.no_grad():
+        for p in blk.parameters():
+            if float(p.abs().max()) == 0.0:
+                p.copy_(torch.randn_like(p) * 0.05)
+    x0 = torch.randn(B, n * n, hidden, device=gpu)
+    c0 = torch.randn(B, 2 * hidden, device=gpu)
+    w = torch.sigmoid(torch.randn(B, n * n, 1, device=gpu))
+    dy = torch.randn(B, n * n, hidden, device=gpu)
+
+    def run(fused):
+        blk.fused_elementwise = fused
+        blk.zero_grad(set_to_none=True)
+        x, c = x0.clone().requires_grad_(True), c0.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=amp, enabled=amp is not None):
+            y = blk(x, c, w)
+        (y.float() * dy).sum().backward()
+        torch.cuda.synchronize()
+        return y.detach().float(), x.grad, c.grad, {k: p.grad.clone() for k, p in blk.named_parameters()}
+
+    try:
+        ya, xa, ca, ga = run(True)
+    finally:
+        blk.fused_elementwise = True
+    yb, xb, cb, gb = run(False)
+    tol = 2e-2 if amp else 2e-5
+    assert torch.isfinite(ya).all() and rel_l2(ya, yb) <= tol
+    assert rel_l2(xa, xb) <= 2 * tol and rel_l2(ca, cb) <= 2 * tol
+    for k in ga:
+        lim = 3 * tol if (amp is None or ga[k].numel() >= 64) else 0.25
+        assert rel_l2(ga[k], gb[k]) <= lim, k
+    blk.fused_elementwise = True
+
+
 def test_graphed_denoiser_matches_eager(gpu):
     """hipGraph replay of the denoiser == eager call, and a full respaced p_sample_loop through it is reproducible."""
     from diffma_amd.diffusion import create_diffusion
