@@ -149,10 +149,7 @@ typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 // 32 bytes per lane written by two instructions at a 32-byte lane stride, halves the instruction count as well but leaves every
 // 32-byte sector half-written per instruction: the forward scan got 7.5 % slower with it.)
 #ifndef DM_CK_ST_AUX
-#define DM_CK_ST_AUX 0         // cache-policy bits of the checkpoint stores / loads (developer A/B: 2 = nt, 1 = sc0, 16 = sc1)
-#endif
-#ifndef DM_CK_LD_AUX
-#define DM_CK_LD_AUX 0
+#define DM_CK_ST_AUX 0         // cache-policy bits of the checkpoint stores (developer A/B: 2 = nt, 1 = sc0, 16 = sc1)
 #endif
 template <int W>
 __device__ __forceinline__ void bio_st_words(const uint32_t (&w)[W], rsrc_t r, int voff, int soff, int gstride) {
@@ -168,7 +165,7 @@ __device__ __forceinline__ void bio_ld_words(uint32_t (&w)[W], rsrc_t r, int vof
     static_assert(W % 4 == 0, "whole 16-byte groups");
 #pragma unroll
     for (int g = 0; g < W / 4; ++g) {
-        const u32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff + g * gstride, DM_CK_LD_AUX);
+        const u32x4_t q = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff + g * gstride, 0);
         w[4 * g] = q[0]; w[4 * g + 1] = q[1]; w[4 * g + 2] = q[2]; w[4 * g + 3] = q[3];
     }
 }

@@ -344,9 +344,7 @@ extern "C" int dm_gemm_large(const dm_gemm_args* args, void* stream) {
     const int mb_x = (g.MB + 7) / 8;                       // whole row blocks per XCD: a row block's column tiles share one L2
     g.TX = mb_x * g.NT;
     hipStream_t st = (hipStream_t)stream;
-    static const bool nt = [] { const char* e = getenv("DM_GL_NT"); return !e || atoi(e) != 0; }();      // DM_GL_NT=0: default-policy C stores (A/B runs)
-    if (a.ab_dtype == DM_BF16 && !nt) hipLaunchKernelGGL((gemm_large_kernel<bf16_t, false>), dim3(256), dim3(GL_THREADS), 0, st, g);
-    else if (a.ab_dtype == DM_BF16) hipLaunchKernelGGL((gemm_large_kernel<bf16_t>), dim3(256), dim3(GL_THREADS), 0, st, g);
+    if (a.ab_dtype == DM_BF16) hipLaunchKernelGGL((gemm_large_kernel<bf16_t>), dim3(256), dim3(GL_THREADS), 0, st, g);
     else hipLaunchKernelGGL((gemm_large_kernel<f16_t>), dim3(256), dim3(GL_THREADS), 0, st, g);
     if (MB_main != MB) {
         dm_gemm_args t = a;

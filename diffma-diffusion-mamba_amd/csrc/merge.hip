@@ -8,15 +8,11 @@
 
 namespace dm {
 
-#ifndef DM_MERGE_NT
-#define DM_MERGE_NT 0          // 1: the streamed 16-byte accesses of merge / gate_bwd carry the nt hint (developer A/B)
-#endif
 // 16-byte (or narrower) vector move of VEC elements
 template <typename T, int VEC>
 __device__ __forceinline__ void vec_ld(T (&tmp)[VEC], const T* src) {
     if constexpr (VEC * sizeof(T) == 16) {
-        if (DM_MERGE_NT) *(f32x4*)tmp = __builtin_nontemporal_load((const f32x4*)src);
-        else *(f32x4*)tmp = *(const f32x4*)src;
+        *(f32x4*)tmp = *(const f32x4*)src;
     } else if constexpr (VEC * sizeof(T) == 8) {
         *(f32x2*)tmp = *(const f32x2*)src;
     } else {
@@ -27,8 +23,7 @@ __device__ __forceinline__ void vec_ld(T (&tmp)[VEC], const T* src) {
 template <typename T, int VEC>
 __device__ __forceinline__ void vec_st(T* dst, const T (&tmp)[VEC]) {
     if constexpr (VEC * sizeof(T) == 16) {
-        if (DM_MERGE_NT) __builtin_nontemporal_store(*(const f32x4*)tmp, (f32x4*)dst);
-        else *(f32x4*)dst = *(const f32x4*)tmp;
+        *(f32x4*)dst = *(const f32x4*)tmp;
     } else if constexpr (VEC * sizeof(T) == 8) {
         *(f32x2*)dst = *(const f32x2*)tmp;
     } else {

@@ -1,7 +1,6 @@
 // C entry point of scan_bwd: validation + dtype dispatch (kernels live in scan_bwd_impl.h / scan_bwd_<dtype>.hip)
 #include "dm_common.h"
 namespace dm {
-constexpr int BWD_CK = 8;
 constexpr int BWD_SUB = 4;     // = checkpoint spacing (scan_bwd_impl.h)
 int scan_bwd_f32(const dm_scan_bwd_args& a, hipStream_t st);
 int scan_bwd_bf16(const dm_scan_bwd_args& a, hipStream_t st);

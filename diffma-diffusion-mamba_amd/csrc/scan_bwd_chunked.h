@@ -16,7 +16,7 @@
 // The dependent chain is ~(0.25 + 1) * L/NW steps instead of L.  dB/dC: a wave owns its steps alone, so the lane sum is
 // finished in the wave (matrix-pipe lane-group sums as in the sequential kernel, then a DPP row sum) and stored as ONE partial
 // row per (step, 64 channels); dA/dD/dbias of the NW waves meet in LDS.  This is the "wavefront-parallel" form of the north
-// star taken where latency, not throughput, is the limit; selection by launch size: dm_scan_bwd_chunked().
+// star taken where latency, not throughput, is the limit; selection by launch size: bwd_chunked_lc().
 #include <cstdlib>
 #include "scan_bwd_impl.h"
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ float row_sum16(float x) {
 template <typename T, typename TBC, bool HAS_Z, bool IDX, int DMODE, int NW, int LC, bool ASH = false>   // DMODE: scan_bwd_impl.h
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void scan_bwd_chunked_kernel(const mix_args<dm_scan_bwd_args> pm) {
     const dm_scan_bwd_args& p = pm.a[blockIdx.z];      // grid.z = congruent launches sharing this one (the two mixers of a block)
-    constexpr int N = 16, NPL = N / 2, SUB = BWD_SUB, M = 2 * N, NSUB = LC / SUB;
+    constexpr int N = 16, NPL = N / 2, SUB = BWD_SUB, M = 2 * N;
     constexpr int ES = (int)sizeof(T);
     constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value;
     static_assert(LC % SUB == 0, "chunks must start on checkpoints");
@@ -380,8 +380,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 // workgroup per CU.
 constexpr int BWD_CHUNKED_NW = 7, BWD_CHUNKED_LC_LONG = 28, BWD_CHUNKED_LC_SHORT = 8;
 static inline int bwd_chunked_lc(int nseq, int dim, int seqlen, int dstate, int flags) {
-    static const int env = [] { const char* e = getenv("DM_SCAN_BWD_CHUNKED"); return e ? atoi(e) : -1; }();   // 0 / 1: developer override
-    const int forced = (flags & DM_FLAG_SCAN_SEQUENTIAL) ? 0 : ((flags & DM_FLAG_SCAN_CHUNKED) ? 1 : env);
+    const int forced = (flags & DM_FLAG_SCAN_SEQUENTIAL) ? 0 : ((flags & DM_FLAG_SCAN_CHUNKED) ? 1 : -1);
     if (forced == 0 || dstate != 16) return 0;
     const int64_t waves = (int64_t)nseq * ((dim + WAVE - 1) / WAVE);
     if (!(waves <= 512 || forced == 1)) return 0;

@@ -35,21 +35,6 @@
 #include <type_traits>
 #include "dm_common.h"
 
-#ifndef DM_K2_HALVES
-#define DM_K2_HALVES 1         // developer A/B: 0 = the whole channel's 16 states in one pass (rounds 3-5)
-#endif
-#ifndef DM_K2_DEFER_WRITE
-#define DM_K2_DEFER_WRITE 0    // developer A/B: 0 = the lane-group totals are written to LDS right behind their MFMAs
-#endif
-#ifndef DM_K2_LDS_AHEAD
-#define DM_K2_LDS_AHEAD 1      // developer A/B: 0 = a step's B / C rows are read at its top, 1 = read ahead in the sweep only, 2 = in the recompute too
-#endif
-#ifndef DM_K2_EXP
-#define DM_K2_EXP 0            // developer timing experiments (bit mask; results are WRONG when non-zero): 1 no dB/dC reduction,
-#endif                         // 2 no barriers / flush, 4 no checkpoint loads, 8 no du / ddelta stores, 16 no LDS B/C re-reads,
-                               // 32 dB/dC products and conversions kept but no MFMA / LDS write / flush, 64 no u / delta / dy loads,
-                               // 128 the two MFMAs of a state group replaced by four XORs (LDS write and flush kept): the MFMAs' own price
-
 namespace dm {
 
 constexpr int BWD_CK = 8;      // steps per staging chunk (B/C rows and dB/dC partials go through LDS once per chunk)
@@ -127,14 +112,6 @@ __device__ __forceinline__ float opaque(float x) {
     asm volatile("" : "+v"(x));
     return x;
 }
-__device__ __forceinline__ uint32_t opaque_u(uint32_t x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ int opaque_i(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 // LDS rows of the staged B / C values are RE-READ at every use instead of being kept in VGPRs across the chunk: the chunk's base
 // address (an LDS pointer in one VGPR) is made opaque to the optimiser once per pass over a sub-chunk (the recompute and the sweep must not share row values: 24
@@ -165,17 +142,16 @@ __device__ __forceinline__ void lds_ld_vec(float (&v)[NS], lds_cfptr row) {
 // softplus(raw + bias) (DM_FLAG_DELTA_ACTIVATED: the producer of delta applied it once per element instead of every scan
 // direction twice); the returned ddelta is the gradient of the RAW value in every mode: softplus'(x) = 1 - exp(-softplus(x)).
 template <typename T, typename TBC, int N, int SPLIT, bool HAS_Z, bool IDX, int DMODE, bool ASH = false>
-__global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu((N / SPLIT <= 8 && N == 16) ? 3 : (N <= 16 ? 2 : 1)))) void scan_bwd_kernel(const dm_scan_bwd_args p) {
+__global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(N <= 16 ? 2 : 1))) void scan_bwd_kernel(const dm_scan_bwd_args p) {
     constexpr int NS = N / SPLIT, NPL = NS / 2, CW = WAVE / SPLIT, CK = BWD_CK, SUB = BWD_SUB, M = 2 * NS, R = M / 4;
     constexpr int ES = (int)sizeof(T);
     constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value && M % 16 == 0;   // dB/dC lane-group sums on the matrix pipe
     // HALVES: the lane's 16 states as two groups of 8 walked one after the other, the recomputed steps' decay factors reused by the sweep
-    constexpr bool HALVES = (DM_K2_HALVES != 0) && MFMA_RED && SPLIT == 1 && N == 16;
+    constexpr bool HALVES = MFMA_RED && SPLIT == 1 && N == 16;
     constexpr int NH = HALVES ? 2 : 1, NPH = NPL / NH;
     constexpr bool CACHE_A = HALVES && !ASH;
     // (the variants with z carry zz[] / sz / ypre as well: the 16 read-ahead registers spill there -- they keep the read at the step's top)
-    constexpr bool LDS_AHEAD = HALVES && !HAS_Z && (DM_K2_LDS_AHEAD != 0), LDS_AHEAD_REC = LDS_AHEAD && (DM_K2_LDS_AHEAD >= 2);
-    constexpr bool DEFER_WRITE = LDS_AHEAD && (DM_K2_DEFER_WRITE != 0);
+    constexpr bool LDS_AHEAD = HALVES && !HAS_Z;
     static_assert(N % SPLIT == 0 && NS % 2 == 0, "d_state/SPLIT must be even");
     static_assert(CK % SUB == 0, "chunk must be a whole number of sub-chunks");
     // lane-group totals of the dB/dC products, one R-float slot per lane; every 16-lane row is shifted by 2R floats so
@@ -275,7 +251,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
     // and store its dB/dC partial rows
     auto flush_dbc = [&](int chunk) {
         const int l0 = chunk * CK;
-        if constexpr (MFMA_RED && SPLIT == 1 && N == 16) {
+        if constexpr (HALVES) {
             // 16-byte reads: a thread owns a QUAD of outputs (4 consecutive registers of a lane slot are 4 consecutive values) and a
             // quarter of the 16 row positions; the four quarter-owners are neighbouring lanes and meet through two quad-permute adds.
             // 16 ds_read_b128 per thread and chunk instead of 64 ds_read_b32 (8 -> 2 LDS instructions per step; the dword form also ran
@@ -296,9 +272,9 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                 acc4[i] = v;
             }
             const float mine = tq == 0 ? acc4[0] : (tq == 1 ? acc4[1] : (tq == 2 ? acc4[2] : acc4[3]));             // value 4 g4 + tq of step j
-            // whole-channel form: value V = column V of [dB 0..15 | dC 0..15].  HALVES: LDS group hf = V >> 4 holds [dB 8hf..8hf+7 | dC 8hf..8hf+7]
+            // LDS group hf = V >> 4 holds [dB 8hf..8hf+7 | dC 8hf..8hf+7]
             const int V = 4 * g4 + tq;
-            const int col = HALVES ? ((V & 8) ? N + 8 * (V >> 4) + (V & 7) : 8 * (V >> 4) + (V & 7)) : V;
+            const int col = (V & 8) ? N + 8 * (V >> 4) + (V & 7) : 8 * (V >> 4) + (V & 7);
             const int vo_p = (l0 + j < L) ? (((l0 + j) * nwg + (int)blockIdx.x) * (2 * N) + col) * 4 : BIO_OOB;
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(mine), r_dbc, vo_p, 0, 0);
             return;
@@ -370,13 +346,13 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
     // full memory latency per 8 steps in s_waitcnt (SQ_WAIT_ANY = 24 % of the wave cycles, the VALU 71 % busy at two waves
     // per SIMD; 15 % and 78 % with the pipeline).  Registers: 12 converted + 12 raw inputs (24 converted before), 3 checkpoint slices (end state | current | next;
     // 5 before with the chunk-level checkpoint prefetch).
-    static_assert(SUB == 4, "row-table entries of a sub-chunk travel as one 4-dword scalar load");
+    static_assert(SUB == 4, "row-table entries of a sub-chunk travel in one 4-entry SGPR vector");
     constexpr int NSC = CK / SUB;
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
     // Four single scalar loads per table and sub-chunk, addresses clamped to the last row, no branch.  (Until round 6 a 4-dword load
     // for whole sub-chunks and the four single loads for the ragged tail were BOTH issued -- hipcc if-converts the choice -- into the
     // same SGPR quad: the write-after-write hazard put an `s_waitcnt lgkmcnt(0)` right behind the first load, a full scalar-memory
-    // latency per table and sub-chunk with the whole wave parked; writing the choice as a real branch parks it at the join instead.)
+    // latency per table and sub-chunk with the whole wave parked.)
     auto load_rows = [&](cptr<int32_t> tab, int ci) -> i32x4_t {          // rows of the steps of sub-chunk ci (clamped to L - 1)
         const int lb = ci < 0 ? 0 : ci * SUB;
         i32x4_t r = {0, 0, 0, 0};
@@ -396,13 +372,12 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
         for (int i = 0; i < SUB; ++i) {
             const int l = (lb + i < L) ? lb + i : L - 1;
-            if (DM_K2_EXP & 64) { ru[i] = (typename bio<T>::raw_t)opaque_u(0x3f00u); rd[i] = (typename bio<T>::raw_t)opaque_u(0x3c23u); rg[i] = (typename bio<T>::raw_t)opaque_u(0x3dccu); if (HAS_Z) rz[i] = 0; continue; }
             ru[i] = bio<T>::ld_raw(r_u, vo, l * sl_u);
             rd[i] = bio<T>::ld_raw(r_dt, vo, l * sl_dt);
             if (HAS_Z) rz[i] = bio<T>::ld_raw(r_z, vo, zrow_is[i] * sl_z);
             rg[i] = bio<T>::ld_raw(r_g, vo, orow_is[i] * sl_g);
         }
-        load_state((DM_K2_EXP & 4) ? -1 : ci, ck_nx);
+        load_state(ci, ck_nx);
         orow_is = load_rows(oidx, ci - 1);
         if (HAS_Z) zrow_is = load_rows(zidx, ci - 1);
     };
@@ -422,9 +397,6 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
     int buf = 0;
     for (int ch = nchunk - 1; ch >= 0; --ch) {
         const int l0 = ch * CK;
-        f32x4 pend = {0.f, 0.f, 0.f, 0.f};                 // DM_K2_DEFER_WRITE: lane-group totals on their way to LDS
-        int pend_off = 0;
-        bool pend_have = false;
         // this chunk's staged rows (the lane's state slice of every row): one LDS address for the whole chunk
         const lds_cfptr bc_chunk = (lds_cfptr)(&bc_lds[0][0][0]) + (buf * CK * 2 * N + q * NS);
         uint32_t bc_next[BC_PER_THREAD];
@@ -465,17 +437,9 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
             for (int hf = 0; hf < NH; ++hf) {
             // one forward step of the group: h <- a*h + B*dl*u   (a kept in `keep` when the sweep will reuse it)
             const lds_cfptr bc_rec = lds_opaque(bc_chunk);
-            float Brn[2 * NPH];                                          // LDS_AHEAD: the B row of the NEXT recomputed step
-            if constexpr (LDS_AHEAD_REC) lds_ld_vec<2 * NPH>(Brn, bc_rec + ((sc * SUB) * 2 * N + hf * 2 * NPH));
             auto fwd_step = [&](f32x2(&h)[NPH], int i, f32x2(&keep)[NPH]) {
                 float Bv[2 * NPH];
                 const lds_cfptr brow = bc_rec + ((sc * SUB + i) * 2 * N + hf * 2 * NPH);          // re-read, do not keep rows in VGPRs
-                if (DM_K2_EXP & 16) { for (int k = 0; k < 2 * NPH; ++k) Bv[k] = opaque(1.0f); } else if constexpr (LDS_AHEAD_REC) {
-#pragma unroll
-                    for (int k = 0; k < 2 * NPH; ++k) Bv[k] = Brn[k];
-                    if (i + 1 < SUB - 1) lds_ld_vec<2 * NPH>(Brn, brow + 2 * N);
-                    __builtin_amdgcn_sched_barrier(0);
-                } else
                 lds_ld_vec<2 * NPH>(Bv, brow);
                 const float dlo = CACHE_A ? dl[i] : opaque(dl[i]);
                 const float du = dlo * uu[i];
@@ -534,7 +498,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                 const int l = valid ? lraw : L - 1;
                 float Bv[2 * NPH], Cv[2 * NPH];
                 const lds_cfptr brow = bc_swp + (j * 2 * N + hf * 2 * NPH);
-                if (DM_K2_EXP & 16) { for (int k = 0; k < 2 * NPH; ++k) { Bv[k] = opaque(1.0f); Cv[k] = opaque(0.5f); } } else if constexpr (LDS_AHEAD) {
+                if constexpr (LDS_AHEAD) {
 #pragma unroll
                     for (int k = 0; k < 2 * NPH; ++k) { Bv[k] = Bn[k]; Cv[k] = Cn[k]; }
                     if (i > 0) {
@@ -543,8 +507,9 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 } else {
-                lds_ld_vec<2 * NPH>(Bv, brow);
-                lds_ld_vec<2 * NPH>(Cv, brow + N); }
+                    lds_ld_vec<2 * NPH>(Bv, brow);
+                    lds_ld_vec<2 * NPH>(Cv, brow + N);
+                }
                 const float g = gg[i];
                 float sz = 1.f, gy = g;
                 if (HAS_Z) {
@@ -611,37 +576,20 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                     dD_acc += gy * uu[i];
                     dbias_acc += ddl;
                 }
-                {
-                    const int vo_s = valid ? vo_st : BIO_OOB;
-                    if (!(DM_K2_EXP & 8) || duv == 123.456f) bio<T>::st_cv(r_du, vo_s, l * sl_du, duv);
-                    if (!(DM_K2_EXP & 8) || ddl == 123.456f) bio<T>::st_cv(r_ddt, vo_s, l * sl_ddt, ddl);
-                    if (HAS_Z) {
-                        const float dzv = g * ypre * sz * (1.0f + zz[i] * (1.0f - sz));
-                        bio<T>::st_cv(r_dz, vo_s, zrow[i] * sl_dz, dzv);
-                    }
+                const int vo_s = valid ? vo_st : BIO_OOB;
+                bio<T>::st_cv(r_du, vo_s, l * sl_du, duv);
+                bio<T>::st_cv(r_ddt, vo_s, l * sl_ddt, ddl);
+                if (HAS_Z) {
+                    const float dzv = g * ypre * sz * (1.0f + zz[i] * (1.0f - sz));
+                    bio<T>::st_cv(r_dz, vo_s, zrow[i] * sl_dz, dzv);
                 }
                 }
-                if constexpr (DM_K2_EXP & 1) {
-                } else if constexpr ((DM_K2_EXP & 32) != 0 && MFMA_RED) {       // products + conversions only: no MFMA, no LDS write (flush: bit 2)
-#pragma unroll
-                    for (int k = 0; k < M / 2 / NH; ++k) asm volatile("" ::"v"(pk_all[k]));
-                } else if constexpr (MFMA_RED && NH == 2) {
+                if constexpr (MFMA_RED && NH == 2) {
                     // this group's 16 values (dB and dC of its 8 states) = ONE pair of MFMAs; LDS group hf (flush_dbc maps the columns)
                     const u32x4_t lo = {pk_all[0], pk_all[1], pk_all[2], pk_all[3]};
                     const u32x4_t hi = {pk_all[4], pk_all[5], pk_all[6], pk_all[7]};
-                    f32x4 dsum;
-                    if constexpr (DM_K2_EXP & 128) dsum = (f32x4){__uint_as_float(lo[0] ^ hi[0]), __uint_as_float(lo[1] ^ hi[1]), __uint_as_float(lo[2] ^ hi[2]), __uint_as_float(lo[3] ^ hi[3])};
-                    else dsum = mfma_group_sum16(sel_lo, sel_hi, lo, hi);
-                    if constexpr (DEFER_WRITE) {
-                        // the totals leave for LDS one group-step LATER: written right behind its MFMAs the ds_write parks the wave until the
-                        // matrix pipe has delivered (the read-ahead fence keeps the MFMAs at the end of the step)
-                        if (pend_have) *reinterpret_cast<f32x4*>(&red_lds[wave][0][0] + pend_off) = pend;
-                        pend = dsum;
-                        pend_off = j * RED_ROW + hf * RED_HALF + red_slot;
-                        pend_have = true;
-                    } else {
-                        *reinterpret_cast<f32x4*>(&red_lds[wave][j][hf * RED_HALF + red_slot]) = dsum;
-                    }
+                    const f32x4 dsum = mfma_group_sum16(sel_lo, sel_hi, lo, hi);
+                    *reinterpret_cast<f32x4*>(&red_lds[wave][j][hf * RED_HALF + red_slot]) = dsum;
                 } else if constexpr (MFMA_RED) {
 #pragma unroll
                     for (int g16 = 0; g16 < M / 16; ++g16) {   // 16 values (8 pairs) per pair of MFMAs; register r of group g16 = value 16*g16 + 4*(lane>>4) + r
@@ -661,11 +609,10 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
             for (int k = 0; k < H0W; ++k) ck_end[k] = ck_cur[k];      // (dead in the HALVES form: removed by the compiler)
         }
-        if (pend_have) *reinterpret_cast<f32x4*>(&red_lds[wave][0][0] + pend_off) = pend;
-        if (!(DM_K2_EXP & 2)) __syncthreads();
-        if (!(DM_K2_EXP & 35)) flush_dbc(ch);
+        __syncthreads();
+        flush_dbc(ch);
         if (ch > 0) stash_bc(buf ^ 1, bc_next);
-        if (!(DM_K2_EXP & 2)) __syncthreads();
+        __syncthreads();
         buf ^= 1;
     }
     if (active) {
@@ -685,10 +632,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 
 // lanes per channel: a whole channel per lane up to d_state 16 (two lanes per channel = 3 waves per SIMD measured +10 % at d_state 16,
 // profiles/r03_k2_experiments.txt), half of one at d_state 32
-#ifndef DM_K2_SPLIT16
-#define DM_K2_SPLIT16 1       // developer A/B: lanes per channel at d_state 16 (2 = half a channel per lane, 3 waves per SIMD)
-#endif
-template <int N> struct bwd_split { static constexpr int value = (N >= 32) ? 2 : (N == 16 ? DM_K2_SPLIT16 : 1); };
+template <int N> struct bwd_split { static constexpr int value = N >= 32 ? 2 : 1; };
 
 template <typename T, typename TBC, int N, bool HAS_Z, bool IDX>
 static void launch_bwd2(const dm_scan_bwd_args& a, hipStream_t st, dim3 grid) {

@@ -1,7 +1,6 @@
 // C entry point of scan_fwd: validation + dtype dispatch (kernels live in scan_fwd_impl.h / scan_fwd_<dtype>.hip)
 #include "dm_common.h"
 namespace dm {
-constexpr int SCAN_PF = 8;
 constexpr int FWD_CKE = 4;      // checkpoint spacing (scan_fwd_impl.h)
 int scan_fwd_f32(const dm_scan_fwd_args& a, hipStream_t st);
 int scan_fwd_bf16(const dm_scan_fwd_args& a, hipStream_t st);

@@ -172,8 +172,7 @@ constexpr int CHUNKED_NW = 14, CHUNKED_LC = 14;          // 14 waves x 14 steps:
 // The 137 KB of LDS allow one workgroup per CU, i.e. 256 at a time: measured (bf16, dim 1024, L 196) 75 -> 24 us at
 // nseq 3, 78 -> 50 us at nseq 24 (two rounds), break-even near nseq 48.
 static inline bool use_chunked_fwd(const dm_scan_fwd_args& a) {
-    static const int env = [] { const char* e = getenv("DM_SCAN_CHUNKED"); return e ? atoi(e) : -1; }();   // 0 / 1: developer override
-    const int forced = (a.flags & DM_FLAG_SCAN_SEQUENTIAL) ? 0 : ((a.flags & DM_FLAG_SCAN_CHUNKED) ? 1 : env);
+    const int forced = (a.flags & DM_FLAG_SCAN_SEQUENTIAL) ? 0 : ((a.flags & DM_FLAG_SCAN_CHUNKED) ? 1 : -1);
     if (forced == 0 || (a.flags & DM_FLAG_OUT_ACCUMULATE)) return false;
     const int64_t waves = (int64_t)a.nseq * ((a.dim + WAVE - 1) / WAVE);
     // checkpoints: built for the two model call patterns only (gated + softplus in the scan; gate and softplus hoisted out of it)

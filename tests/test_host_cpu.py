@@ -428,21 +428,32 @@ def test_staged_backward_equals_one_backward():
         mamba_mod.spiral_ssm = real
 
 
+_LLVM_TOOLS = [os.path.join("/opt/rocm/lib/llvm/bin", t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump")]
+
+
+def _gfx950_disassembly(obj, tmp_path):
+    """`llvm-objdump -d` of the gfx950 code object inside a built .o; None for a host-only object.  The section dump names an output
+    file (the null device): without one llvm-objcopy writes the object back in place."""
+    import subprocess
+    fat, co = str(tmp_path / "x.fat"), str(tmp_path / "x.co")
+    if subprocess.run([_LLVM_TOOLS[0], f"--dump-section=.hip_fatbin={fat}", obj, os.devnull], capture_output=True).returncode != 0 or not os.path.isfile(fat):
+        return None
+    subprocess.run([_LLVM_TOOLS[1], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
+    os.remove(fat)
+    return subprocess.run([_LLVM_TOOLS[2], "-d", co], check=True, capture_output=True, text=True).stdout
+
+
 def test_slab_kernel_broadcasts_from_the_low_dword_only(tmp_path):
     """K4x slab form, DESIGN.md section 3: `float2 * float` must broadcast the LOW dword of the register pair the row-table read
     returns (op_sel_hi).  With the table entry laid out {acc_off, own} hipcc emitted `v_pk_mul_f32 ... op_sel:[1,0]` (low result
     from the HIGH dword) and the kernel miscounted single rows on MI355X now and then.  The built object must not contain that form
     in the slab kernel (a compiler or source change that brings it back fails here, on the CPU, instead of sporadically on a GPU)."""
-    import re, shutil, subprocess
-    llvm = "/opt/rocm/lib/llvm/bin"
+    import re
     obj = os.path.join(ROOT, "diffma-diffusion-mamba_amd", "csrc", "conv_xproj.o")
-    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump")]
-    if not os.path.isfile(obj) or not all(os.path.isfile(t) for t in tools):
+    if not os.path.isfile(obj) or not all(os.path.isfile(t) for t in _LLVM_TOOLS):
         pytest.skip("needs the built conv_xproj.o and the ROCm llvm tools")
-    fat, co = str(tmp_path / "x.fat"), str(tmp_path / "x.co")
-    subprocess.run([tools[0], f"--dump-section=.hip_fatbin={fat}", obj], check=True)
-    subprocess.run([tools[1], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-    dis = subprocess.run([tools[2], "-d", co], check=True, capture_output=True, text=True).stdout
+    dis = _gfx950_disassembly(obj, tmp_path)
+    assert dis is not None, "conv_xproj.o holds no device code"
     name, seen, bad = None, 0, []
     for line in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)
@@ -464,21 +475,16 @@ def test_no_matrix_pipe_kernel_takes_a_packed_low_result_from_src1_high(tmp_path
     pair, an early-clobber destination); the same selection on SRC0, the low-dword broadcast and two plain multiplies are clean.
     Kernels without MFMAs carry hundreds of these forms and pass every test.  So: no object of the library that contains v_mfma may
     contain a packed fp32 instruction whose op_sel sets the src1 bit."""
-    import glob, re, subprocess
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump")]
+    import glob, re
     objs = sorted(glob.glob(os.path.join(ROOT, "diffma-diffusion-mamba_amd", "csrc", "*.o")))
-    if not objs or not all(os.path.isfile(t) for t in tools):
+    if not objs or not all(os.path.isfile(t) for t in _LLVM_TOOLS):
         pytest.skip("needs the built objects and the ROCm llvm tools")
     risky = re.compile(r"v_pk_(mul|add)_f32.*op_sel:\[[01],1\]|v_pk_fma_f32.*op_sel:\[[01],1,[01]\]")
     checked, bad = 0, {}
     for obj in objs:
-        fat, co = str(tmp_path / "x.fat"), str(tmp_path / "x.co")
-        if subprocess.run([tools[0], f"--dump-section=.hip_fatbin={fat}", obj], capture_output=True).returncode != 0 or not os.path.isfile(fat):
+        dis = _gfx950_disassembly(obj, tmp_path)
+        if dis is None:
             continue                                                    # host-only object
-        subprocess.run([tools[1], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-        dis = subprocess.run([tools[2], "-d", co], check=True, capture_output=True, text=True).stdout
-        os.remove(fat)
         name, per = None, {}
         for line in dis.splitlines():
             m = re.match(r"^[0-9a-f]+ <(.*)>:$", line)

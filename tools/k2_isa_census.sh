@@ -6,7 +6,7 @@ OBJ=${1:-$CS/scan_bwd_bf16.o}
 PAT=${2:-'scan_bwd_kernelINS_6bf16_tES1_Li16ELi1ELb0ELb1ELi2ELb0E'}
 TMP=$(mktemp -d)
 BIN=/opt/rocm/lib/llvm/bin
-$BIN/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $OBJ
+$BIN/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $OBJ /dev/null     # (no output file: the object is rewritten in place)
 $BIN/clang-offload-bundler --unbundle --type=o --input=$TMP/fat.bin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$TMP/dev.co
 $BIN/llvm-objdump -d --no-show-raw-insn $TMP/dev.co | awk -v pat="$PAT" '
   /^[0-9a-f]+ <.*>:$/ { on = ($0 ~ pat) }

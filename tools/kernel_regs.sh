@@ -7,7 +7,7 @@ OBJ=$CS/${1:-scan_bwd_bf16}.o
 PAT=${2:-.}
 TMP=$(mktemp -d)
 BIN=/opt/rocm/lib/llvm/bin
-$BIN/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $OBJ
+$BIN/llvm-objcopy --dump-section .hip_fatbin=$TMP/fat.bin $OBJ /dev/null     # (no output file: the object is rewritten in place)
 $BIN/clang-offload-bundler --unbundle --type=o --input=$TMP/fat.bin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$TMP/dev.co
 $BIN/llvm-readelf --notes $TMP/dev.co | PAT="$PAT" python3 -c "
 import sys, re, os, subprocess
