@@ -252,10 +252,10 @@ static inline bool even4(const void* ptr, std::initializer_list<int64_t> strides
 }
 
 template <typename T, typename TW, int W, int VEC>
-static void launch_conv_fwd_v(const dm_conv_fwd_args& a, hipStream_t st) {
+static void launch_conv_fwd_v(const dm_conv_fwd_args& a, const dm_conv_fwd_args* second, hipStream_t st) {
     const int nchunk = (a.seqlen + CONV_CH - 1) / CONV_CH;
     unsigned gz;
-    const mix_args<dm_conv_fwd_args> m = mix_make(a, gz);
+    const mix_args<dm_conv_fwd_args> m = mix_make(a, second, gz);
     dim3 grid((a.dim + WAVE * VEC - 1) / (WAVE * VEC), nchunk, a.ndir * a.batch * gz), block(WAVE);
     if (a.flags & DM_FLAG_SILU)
         hipLaunchKernelGGL((conv_fwd_kernel<T, TW, W, true, VEC>), grid, block, 0, st, m);
@@ -264,12 +264,12 @@ static void launch_conv_fwd_v(const dm_conv_fwd_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TW, int W>
-static int launch_conv_fwd(const dm_conv_fwd_args& a, hipStream_t st) {
+static int launch_conv_fwd(const dm_conv_fwd_args& a, const dm_conv_fwd_args* second, hipStream_t st) {
     if constexpr (sizeof(T) == 2) {
-        if (even4(a.x, {a.x_sb, a.x_sl}, a.dim) && even4(a.out, {a.o_ss, a.o_sl}, a.dim)) launch_conv_fwd_v<T, TW, W, 2>(a, st);
-        else launch_conv_fwd_v<T, TW, W, 1>(a, st);
+        if (even4(a.x, {a.x_sb, a.x_sl}, a.dim) && even4(a.out, {a.o_ss, a.o_sl}, a.dim)) launch_conv_fwd_v<T, TW, W, 2>(a, second, st);
+        else launch_conv_fwd_v<T, TW, W, 1>(a, second, st);
     } else {
-        launch_conv_fwd_v<T, TW, W, 1>(a, st);
+        launch_conv_fwd_v<T, TW, W, 1>(a, second, st);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dm_gather_conv1d_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
@@ -277,9 +277,9 @@ static int launch_conv_fwd(const dm_conv_fwd_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TW, int W, int VEC>
-static void launch_conv_bwd_v(const dm_conv_bwd_args& a, hipStream_t st) {
+static void launch_conv_bwd_v(const dm_conv_bwd_args& a, const dm_conv_bwd_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_conv_bwd_args> m = mix_make(a, gz);
+    const mix_args<dm_conv_bwd_args> m = mix_make(a, second, gz);
     dim3 grid((a.dim + WAVE * VEC - 1) / (WAVE * VEC), a.nchunk, a.ndir * a.batch * gz), block(WAVE * CONV_BWD_WAVES);
     if (a.flags & DM_FLAG_SILU)
         hipLaunchKernelGGL((conv_bwd_kernel<T, TW, W, true, VEC>), grid, block, 0, st, m);
@@ -288,40 +288,89 @@ static void launch_conv_bwd_v(const dm_conv_bwd_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TW, int W>
-static int launch_conv_bwd(const dm_conv_bwd_args& a, hipStream_t st) {
+static int launch_conv_bwd(const dm_conv_bwd_args& a, const dm_conv_bwd_args* second, hipStream_t st) {
     if constexpr (sizeof(T) == 2) {
         if (even4(a.x, {a.x_sb, a.x_sl}, a.dim) && even4(a.dout, {a.do_ss, a.do_sl}, a.dim) && even4(a.dx, {a.dx_ss, a.dx_sl}, a.dim))
-            launch_conv_bwd_v<T, TW, W, 2>(a, st);
+            launch_conv_bwd_v<T, TW, W, 2>(a, second, st);
         else
-            launch_conv_bwd_v<T, TW, W, 1>(a, st);
+            launch_conv_bwd_v<T, TW, W, 1>(a, second, st);
     } else {
-        launch_conv_bwd_v<T, TW, W, 1>(a, st);
+        launch_conv_bwd_v<T, TW, W, 1>(a, second, st);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dm_gather_conv1d_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
     return DM_OK;
 }
 
-template <typename T, typename TW, typename Args, int (*F2)(const Args&, hipStream_t), int (*F3)(const Args&, hipStream_t),
-          int (*F4)(const Args&, hipStream_t)>
-static int by_width(const Args& a, hipStream_t st, const char* who) {
+template <typename T, typename TW, typename Args, int (*F2)(const Args&, const Args*, hipStream_t),
+          int (*F3)(const Args&, const Args*, hipStream_t), int (*F4)(const Args&, const Args*, hipStream_t)>
+static int by_width(const Args& a, const Args* second, hipStream_t st, const char* who) {
     switch (a.width) {
-        case 2: return F2(a, st);
-        case 3: return F3(a, st);
-        case 4: return F4(a, st);
+        case 2: return F2(a, second, st);
+        case 3: return F3(a, second, st);
+        case 4: return F4(a, second, st);
         default: set_error("%s: width %d not in {2,3,4}", who, a.width); return DM_ERR_ARG;
     }
 }
 
 template <typename T, typename TW>
-static int conv_fwd_t(const dm_conv_fwd_args& a, hipStream_t st) {
+static int conv_fwd_t(const dm_conv_fwd_args& a, const dm_conv_fwd_args* second, hipStream_t st) {
     return by_width<T, TW, dm_conv_fwd_args, launch_conv_fwd<T, TW, 2>, launch_conv_fwd<T, TW, 3>,
-                    launch_conv_fwd<T, TW, 4>>(a, st, "dm_gather_conv1d_fwd");
+                    launch_conv_fwd<T, TW, 4>>(a, second, st, "dm_gather_conv1d_fwd");
 }
 template <typename T, typename TW>
-static int conv_bwd_t(const dm_conv_bwd_args& a, hipStream_t st) {
+static int conv_bwd_t(const dm_conv_bwd_args& a, const dm_conv_bwd_args* second, hipStream_t st) {
     return by_width<T, TW, dm_conv_bwd_args, launch_conv_bwd<T, TW, 2>, launch_conv_bwd<T, TW, 3>,
-                    launch_conv_bwd<T, TW, 4>>(a, st, "dm_gather_conv1d_bwd");
+                    launch_conv_bwd<T, TW, 4>>(a, second, st, "dm_gather_conv1d_bwd");
+}
+
+static int check_conv_fwd(const dm_conv_fwd_args& a) {
+    if (!a.x || !a.weight || !a.out) { set_error("dm_gather_conv1d_fwd: null tensor pointer"); return DM_ERR_ARG; }
+    if (a.batch <= 0 || a.dim <= 0 || a.seqlen <= 0 || a.ndir <= 0) { set_error("dm_gather_conv1d_fwd: non-positive size"); return DM_ERR_ARG; }
+    if ((int64_t)a.ndir * a.batch * DM_MAX_MIX > 65535) { set_error("dm_gather_conv1d_fwd: ndir*batch > 32767"); return DM_ERR_ARG; }
+    if (a.ndir > 1 && !a.row_index) { set_error("dm_gather_conv1d_fwd: ndir>1 needs row_index"); return DM_ERR_ARG; }
+    if (a.x_sd != 1 || a.o_sd != 1) { set_error("dm_gather_conv1d_fwd: needs token-major tensors (channel stride 1)"); return DM_ERR_LAYOUT; }
+    if (a.w_dtype != DM_F32 && a.w_dtype != a.io_dtype) { set_error("dm_gather_conv1d_fwd: w_dtype must be fp32 or io_dtype"); return DM_ERR_DTYPE; }
+    return DM_OK;
+}
+static bool pairs_conv_fwd(const dm_conv_fwd_args& x, const dm_conv_fwd_args& y) {
+    return same_align4(x.x, y.x) && same_align4(x.out, y.out) &&      // the 2-channel form is chosen per pointer
+           mix_congruent(x, y, &dm_conv_fwd_args::x, &dm_conv_fwd_args::weight, &dm_conv_fwd_args::bias, &dm_conv_fwd_args::row_index,
+                         &dm_conv_fwd_args::out);
+}
+static int run_conv_fwd(const dm_conv_fwd_args& a, const dm_conv_fwd_args* second, hipStream_t st) {
+    const bool wf32 = a.w_dtype == DM_F32;
+    switch (a.io_dtype) {
+        case DM_F32: return conv_fwd_t<float, float>(a, second, st);
+        case DM_BF16: return wf32 ? conv_fwd_t<bf16_t, float>(a, second, st) : conv_fwd_t<bf16_t, bf16_t>(a, second, st);
+        case DM_F16: return wf32 ? conv_fwd_t<f16_t, float>(a, second, st) : conv_fwd_t<f16_t, f16_t>(a, second, st);
+        default: set_error("dm_gather_conv1d_fwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
+    }
+}
+
+static int check_conv_bwd(const dm_conv_bwd_args& a) {
+    if (!a.x || !a.weight || !a.dout || !a.dx || !a.dw_partial) { set_error("dm_gather_conv1d_bwd: null tensor pointer"); return DM_ERR_ARG; }
+    if (a.batch <= 0 || a.dim <= 0 || a.seqlen <= 0 || a.ndir <= 0) { set_error("dm_gather_conv1d_bwd: non-positive size"); return DM_ERR_ARG; }
+    if ((int64_t)a.ndir * a.batch * DM_MAX_MIX > 65535) { set_error("dm_gather_conv1d_bwd: ndir*batch > 32767"); return DM_ERR_ARG; }
+    if (a.ndir > 1 && !a.row_index) { set_error("dm_gather_conv1d_bwd: ndir>1 needs row_index"); return DM_ERR_ARG; }
+    if (a.nchunk != dm_conv_nchunk(a.seqlen)) { set_error("dm_gather_conv1d_bwd: nchunk must be dm_conv_nchunk(seqlen)"); return DM_ERR_ARG; }
+    if (a.x_sd != 1 || a.do_sd != 1 || a.dx_sd != 1) { set_error("dm_gather_conv1d_bwd: needs token-major tensors"); return DM_ERR_LAYOUT; }
+    if (a.w_dtype != DM_F32 && a.w_dtype != a.io_dtype) { set_error("dm_gather_conv1d_bwd: w_dtype must be fp32 or io_dtype"); return DM_ERR_DTYPE; }
+    return DM_OK;
+}
+static bool pairs_conv_bwd(const dm_conv_bwd_args& x, const dm_conv_bwd_args& y) {
+    return same_align4(x.x, y.x) && same_align4(x.dout, y.dout) && same_align4(x.dx, y.dx) &&      // the 2-channel form is chosen per pointer
+           mix_congruent(x, y, &dm_conv_bwd_args::x, &dm_conv_bwd_args::weight, &dm_conv_bwd_args::bias, &dm_conv_bwd_args::row_index,
+                         &dm_conv_bwd_args::dout, &dm_conv_bwd_args::dx, &dm_conv_bwd_args::dw_partial, &dm_conv_bwd_args::db_partial);
+}
+static int run_conv_bwd(const dm_conv_bwd_args& a, const dm_conv_bwd_args* second, hipStream_t st) {
+    const bool wf32 = a.w_dtype == DM_F32;
+    switch (a.io_dtype) {
+        case DM_F32: return conv_bwd_t<float, float>(a, second, st);
+        case DM_BF16: return wf32 ? conv_bwd_t<bf16_t, float>(a, second, st) : conv_bwd_t<bf16_t, bf16_t>(a, second, st);
+        case DM_F16: return wf32 ? conv_bwd_t<f16_t, float>(a, second, st) : conv_bwd_t<f16_t, f16_t>(a, second, st);
+        default: set_error("dm_gather_conv1d_bwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
+    }
 }
 
 }  // namespace dm
@@ -335,66 +384,21 @@ extern "C" int dm_conv_nchunk(int seqlen) {
 extern "C" int dm_gather_conv1d_fwd(const dm_conv_fwd_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_gather_conv1d_fwd: null args"); return DM_ERR_ARG; }
-    const dm_conv_fwd_args& a = *args;
-    if (!a.x || !a.weight || !a.out) { set_error("dm_gather_conv1d_fwd: null tensor pointer"); return DM_ERR_ARG; }
-    if (a.batch <= 0 || a.dim <= 0 || a.seqlen <= 0 || a.ndir <= 0) { set_error("dm_gather_conv1d_fwd: non-positive size"); return DM_ERR_ARG; }
-    if ((int64_t)a.ndir * a.batch * DM_MAX_MIX > 65535) { set_error("dm_gather_conv1d_fwd: ndir*batch > 32767"); return DM_ERR_ARG; }
-    if (a.ndir > 1 && !a.row_index) { set_error("dm_gather_conv1d_fwd: ndir>1 needs row_index"); return DM_ERR_ARG; }
-    if (a.x_sd != 1 || a.o_sd != 1) { set_error("dm_gather_conv1d_fwd: needs token-major tensors (channel stride 1)"); return DM_ERR_LAYOUT; }
-    hipStream_t st = (hipStream_t)stream;
-    const bool wf32 = a.w_dtype == DM_F32;
-    if (!wf32 && a.w_dtype != a.io_dtype) { set_error("dm_gather_conv1d_fwd: w_dtype must be fp32 or io_dtype"); return DM_ERR_DTYPE; }
-    switch (a.io_dtype) {
-        case DM_F32: return conv_fwd_t<float, float>(a, st);
-        case DM_BF16: return wf32 ? conv_fwd_t<bf16_t, float>(a, st) : conv_fwd_t<bf16_t, bf16_t>(a, st);
-        case DM_F16: return wf32 ? conv_fwd_t<f16_t, float>(a, st) : conv_fwd_t<f16_t, f16_t>(a, st);
-        default: set_error("dm_gather_conv1d_fwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
-    }
+    const int rc = check_conv_fwd(*args);
+    return rc ? rc : run_conv_fwd(*args, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int dm_gather_conv1d_bwd(const dm_conv_bwd_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_gather_conv1d_bwd: null args"); return DM_ERR_ARG; }
-    const dm_conv_bwd_args& a = *args;
-    if (!a.x || !a.weight || !a.dout || !a.dx || !a.dw_partial) { set_error("dm_gather_conv1d_bwd: null tensor pointer"); return DM_ERR_ARG; }
-    if (a.batch <= 0 || a.dim <= 0 || a.seqlen <= 0 || a.ndir <= 0) { set_error("dm_gather_conv1d_bwd: non-positive size"); return DM_ERR_ARG; }
-    if ((int64_t)a.ndir * a.batch * DM_MAX_MIX > 65535) { set_error("dm_gather_conv1d_bwd: ndir*batch > 32767"); return DM_ERR_ARG; }
-    if (a.ndir > 1 && !a.row_index) { set_error("dm_gather_conv1d_bwd: ndir>1 needs row_index"); return DM_ERR_ARG; }
-    if (a.nchunk != dm_conv_nchunk(a.seqlen)) { set_error("dm_gather_conv1d_bwd: nchunk must be dm_conv_nchunk(seqlen)"); return DM_ERR_ARG; }
-    if (a.x_sd != 1 || a.do_sd != 1 || a.dx_sd != 1) { set_error("dm_gather_conv1d_bwd: needs token-major tensors"); return DM_ERR_LAYOUT; }
-    hipStream_t st = (hipStream_t)stream;
-    const bool wf32 = a.w_dtype == DM_F32;
-    if (!wf32 && a.w_dtype != a.io_dtype) { set_error("dm_gather_conv1d_bwd: w_dtype must be fp32 or io_dtype"); return DM_ERR_DTYPE; }
-    switch (a.io_dtype) {
-        case DM_F32: return conv_bwd_t<float, float>(a, st);
-        case DM_BF16: return wf32 ? conv_bwd_t<bf16_t, float>(a, st) : conv_bwd_t<bf16_t, bf16_t>(a, st);
-        case DM_F16: return wf32 ? conv_bwd_t<f16_t, float>(a, st) : conv_bwd_t<f16_t, f16_t>(a, st);
-        default: set_error("dm_gather_conv1d_bwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
-    }
+    const int rc = check_conv_bwd(*args);
+    return rc ? rc : run_conv_bwd(*args, nullptr, (hipStream_t)stream);
 }
 
-// ---- n congruent launches in one (the two mixers of a block at small batch) ------------------------------------------------
-static inline bool same_align4(const void* x, const void* y) { return (((uintptr_t)x ^ (uintptr_t)y) & 3) == 0; }
-
+// ---- n congruent launches in one (the two mixers of a block at small batch; see dm_common.h mix_run_n) -----------------------
 extern "C" int dm_gather_conv1d_fwd_n(const dm_conv_fwd_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_gather_conv1d_fwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_conv_fwd_args* a) { return dm_gather_conv1d_fwd(a, stream); },
-                        [](const dm_conv_fwd_args& x, const dm_conv_fwd_args& y) {
-                            return same_align4(x.x, y.x) && same_align4(x.out, y.out) &&      // the 2-channel form is chosen per pointer
-                                   mix_congruent(x, y, &dm_conv_fwd_args::x, &dm_conv_fwd_args::weight, &dm_conv_fwd_args::bias,
-                                                 &dm_conv_fwd_args::row_index, &dm_conv_fwd_args::out);
-                        });
+    return dm::mix_run_n("dm_gather_conv1d_fwd_n", args, n, stream, dm::check_conv_fwd, dm::pairs_conv_fwd, dm::run_conv_fwd);
 }
-
 extern "C" int dm_gather_conv1d_bwd_n(const dm_conv_bwd_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_gather_conv1d_bwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_conv_bwd_args* a) { return dm_gather_conv1d_bwd(a, stream); },
-                        [](const dm_conv_bwd_args& x, const dm_conv_bwd_args& y) {
-                            return same_align4(x.x, y.x) && same_align4(x.dout, y.dout) && same_align4(x.dx, y.dx) &&
-                                   mix_congruent(x, y, &dm_conv_bwd_args::x, &dm_conv_bwd_args::weight, &dm_conv_bwd_args::bias,
-                                                 &dm_conv_bwd_args::row_index, &dm_conv_bwd_args::dout, &dm_conv_bwd_args::dx,
-                                                 &dm_conv_bwd_args::dw_partial, &dm_conv_bwd_args::db_partial);
-                        });
+    return dm::mix_run_n("dm_gather_conv1d_bwd_n", args, n, stream, dm::check_conv_bwd, dm::pairs_conv_bwd, dm::run_conv_bwd);
 }

@@ -22,43 +22,39 @@ template <typename A> struct mix_args {
     A a[DM_MAX_MIX];
     int n;
 };
-// Host side: a dm_*_n entry point announces the second argument struct before it runs the ordinary single-launch path on the
-// first; the launch site of a mix-capable kernel takes it (mix_make) -- any other launch site leaves it, and the entry point
-// then launches the second struct on its own.  Thread-local: the backward runs on autograd's worker thread.
-const void* mix_peek();
-void mix_announce(const void* second);
-bool mix_was_taken();
-void mix_take();
-template <typename A> static inline mix_args<A> mix_make(const A& a, unsigned& gz) {
+// Host side: every pair-capable operator has three pieces, and the second struct travels between them as a plain argument:
+//   check(a)            the argument checks of the single entry point (status + message), no launch;
+//   pairs(x, y)         pure: the structs are congruent, select the same kernel instantiation, and the kernel family their shape
+//                       selects takes two structs;
+//   run(a, second, st)  dispatch and launch; `second` (nullptr for a single launch) goes down to mix_make at the launch site.  A
+//                       code path that takes one struct only has no `second` parameter.
+// The single entry point is null check, check, run(a, nullptr, st); the dm_*_n entry point is mix_run_n.
+void set_error(const char* fmt, ...);        // thread-local error string (capi.hip)
+template <typename A> static inline mix_args<A> mix_make(const A& a, const A* second, unsigned& gz) {
     mix_args<A> m;
     m.a[0] = a;
-    const A* second = static_cast<const A*>(mix_peek());
-    if (second) {
-        m.a[1] = *second;
-        m.n = 2;
-        mix_take();
-    } else {
-        m.a[1] = a;
-        m.n = 1;
-    }
+    m.a[1] = second ? *second : a;
+    m.n = second ? 2 : 1;
     gz = (unsigned)m.n;
     return m;
 }
-// launch loop of a dm_*_n entry point: congruent neighbours share a launch when the kernel their shape selects can take two
-template <typename A, typename F, typename C>
-static inline int mix_launch_n(const A* args, int n, F single, C congruent) {
-    int i = 0;
-    while (i < n) {
-        const bool pair = i + 1 < n && congruent(args[i], args[i + 1]);
-        mix_announce(pair ? &args[i + 1] : nullptr);
-        const int rc = single(&args[i]);
-        const bool taken = mix_was_taken();
-        mix_announce(nullptr);
+// dm_*_n: the result of the single entry point on args[0], args[1], ... in order, stopping at the first non-zero status.  A
+// neighbour shares the launch of args[i] only if it passes its own check and pairs holds; otherwise it waits for its own turn.
+template <typename A, typename Check, typename Pairs, typename Run>
+static inline int mix_run_n(const char* who, const A* args, int n, void* stream, Check check, Pairs pairs, Run run) {
+    if (!args || n <= 0) { set_error("%s: null args / n <= 0", who); return DM_ERR_ARG; }
+    for (int i = 0; i < n;) {
+        int rc = check(args[i]);
         if (rc != 0) return rc;
-        i += (pair && taken) ? 2 : 1;
+        const bool pair = i + 1 < n && check(args[i + 1]) == 0 && pairs(args[i], args[i + 1]);
+        rc = run(args[i], pair ? &args[i + 1] : nullptr, (hipStream_t)stream);
+        if (rc != 0) return rc;
+        i += pair ? 2 : 1;
     }
     return 0;
 }
+static inline bool same_align16(const void* x, const void* y) { return (((uintptr_t)x ^ (uintptr_t)y) & 15) == 0; }
+static inline bool same_align4(const void* x, const void* y) { return (((uintptr_t)x ^ (uintptr_t)y) & 3) == 0; }
 // all fields equal except the listed pointer members, whose null-ness must agree
 template <typename A, typename... M>
 static inline bool mix_congruent(const A& x, const A& y, M A::*... ptrs) {
@@ -274,9 +270,6 @@ __device__ __forceinline__ float sigmoid_f(float x) {
     return fast_rcp(1.0f + fast_exp2(-x * LOG2E));
 }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
-
-// thread-local error string (host side)
-void set_error(const char* fmt, ...);
 
 // Sum over the 64 lanes of a wave on the VALU's DPP path (every lane gets the total): 4 in-row butterfly steps, two
 // row broadcasts and one readlane, instead of 6 ds_bpermute round trips through the LDS pipe (__shfl_xor).

@@ -142,16 +142,7 @@ __global__ __launch_bounds__(64 * DTP_WAVES) void dtproj_softplus_kernel(const m
     }
 }
 
-}  // namespace dm
-
-extern "C" int dm_dtproj_softplus_supported(int dim, int rank, int io_dtype) {
-    return (io_dtype == DM_BF16 || io_dtype == DM_F16) && dim > 0 && dim % 16 == 0 && rank > 0 && rank <= 32 && rank % 8 == 0;
-}
-
-extern "C" int dm_dtproj_softplus_fwd(const dm_dtproj_args* args, void* stream) {
-    using namespace dm;
-    if (!args) { set_error("dm_dtproj_softplus_fwd: null args"); return DM_ERR_ARG; }
-    const dm_dtproj_args& a = *args;
+static int check_dtproj_fwd(const dm_dtproj_args& a) {
     if (!a.xdbl || !a.w || !a.delta) { set_error("dm_dtproj_softplus_fwd: null tensor pointer"); return DM_ERR_ARG; }
     if (a.rows <= 0 || a.dim <= 0 || a.rank <= 0) { set_error("dm_dtproj_softplus_fwd: non-positive size"); return DM_ERR_ARG; }
     if (!dm_dtproj_softplus_supported(a.dim, a.rank, a.io_dtype)) {
@@ -161,18 +152,36 @@ extern "C" int dm_dtproj_softplus_fwd(const dm_dtproj_args* args, void* stream) 
     if (a.xd_sr % 8 != 0 || a.xd_sr < a.rank || ((uintptr_t)a.xdbl % 16) || ((uintptr_t)a.w % 16) || ((uintptr_t)a.delta % 16)) {
         set_error("dm_dtproj_softplus_fwd: x_dbl row stride must be a multiple of 8 elements and all tensors 16-byte aligned"); return DM_ERR_LAYOUT;
     }
+    if ((a.dim + DTP_WAVES * DTP_NQ * 64 - 1) / (DTP_WAVES * DTP_NQ * 64) > 65535) { set_error("dm_dtproj_softplus_fwd: dim too large"); return DM_ERR_ARG; }
+    return DM_OK;
+}
+static bool pairs_dtproj_fwd(const dm_dtproj_args& x, const dm_dtproj_args& y) {
+    return mix_congruent(x, y, &dm_dtproj_args::xdbl, &dm_dtproj_args::w, &dm_dtproj_args::bias, &dm_dtproj_args::delta);
+}
+static int run_dtproj_fwd(const dm_dtproj_args& a, const dm_dtproj_args* second, hipStream_t st) {
     const int tiles = (a.rows + 15) / 16;
     unsigned gz;
-    const mix_args<dm_dtproj_args> m = mix_make(a, gz);
+    const mix_args<dm_dtproj_args> m = mix_make(a, second, gz);
     dim3 grid((tiles + DTP_TILES - 1) / DTP_TILES, (a.dim + DTP_WAVES * DTP_NQ * 64 - 1) / (DTP_WAVES * DTP_NQ * 64), gz);
     for (int tpw = DTP_TILES / 2; tpw >= 1 && grid.x * grid.y * gz < 512; tpw /= 2) grid.x = (tiles + tpw - 1) / tpw;     // fewer tiles per workgroup until the chip is covered twice
-    if (grid.y > 65535) { set_error("dm_dtproj_softplus_fwd: dim too large"); return DM_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream;
     if (a.io_dtype == DM_BF16) hipLaunchKernelGGL((dtproj_softplus_kernel<bf16_t>), grid, dim3(64 * DTP_WAVES), 0, st, m);
     else hipLaunchKernelGGL((dtproj_softplus_kernel<f16_t>), grid, dim3(64 * DTP_WAVES), 0, st, m);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dm_dtproj_softplus_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
     return DM_OK;
+}
+
+}  // namespace dm
+
+extern "C" int dm_dtproj_softplus_supported(int dim, int rank, int io_dtype) {
+    return (io_dtype == DM_BF16 || io_dtype == DM_F16) && dim > 0 && dim % 16 == 0 && rank > 0 && rank <= 32 && rank % 8 == 0;
+}
+
+extern "C" int dm_dtproj_softplus_fwd(const dm_dtproj_args* args, void* stream) {
+    using namespace dm;
+    if (!args) { set_error("dm_dtproj_softplus_fwd: null args"); return DM_ERR_ARG; }
+    const int rc = check_dtproj_fwd(*args);
+    return rc ? rc : run_dtproj_fwd(*args, nullptr, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -347,9 +356,9 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
 }
 
 template <typename T>
-static int dtproj_bwd_launch(const dm_dtproj_bwd_args& a, hipStream_t st) {
+static int dtproj_bwd_launch(const dm_dtproj_bwd_args& a, const dm_dtproj_bwd_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_dtproj_bwd_args> m = mix_make(a, gz);
+    const mix_args<dm_dtproj_bwd_args> m = mix_make(a, second, gz);
     const dim3 grid((unsigned)a.nblk, 1, gz), block(64 * DTB_WAVES);
     const int kc = a.dim / (32 * DTB_WAVES), nr = a.rank / 16;
 #define DM_DTB(KC, NR) hipLaunchKernelGGL((dtproj_bwd_kernel<T, KC, NR>), grid, block, 0, st, m)
@@ -366,6 +375,29 @@ static int dtproj_bwd_launch(const dm_dtproj_bwd_args& a, hipStream_t st) {
     return DM_OK;
 }
 
+static int check_dtproj_bwd(const dm_dtproj_bwd_args& a) {
+    if (!a.ddelta || !a.xdbl || !a.w || !a.dxdbl || !a.part) { set_error("dm_dtproj_bwd: null tensor pointer"); return DM_ERR_ARG; }
+    if (!dm_dtproj_bwd_supported(a.dim, a.rank, a.io_dtype)) { set_error("dm_dtproj_bwd: unsupported dim %d / rank %d / dtype %d", a.dim, a.rank, a.io_dtype); return DM_ERR_ARG; }
+    if (a.rows <= 0) { set_error("dm_dtproj_bwd: rows (%d) must be positive", a.rows); return DM_ERR_ARG; }
+    if (a.nblk <= 0 || a.nblk > (a.rows + DTB_TM - 1) / DTB_TM) { set_error("dm_dtproj_bwd: nblk (%d) must be in 1 .. ceil(rows / %d)", a.nblk, DTB_TM); return DM_ERR_ARG; }
+    if (a.xd_sr % 8 != 0 || a.dxd_sr % 4 != 0 || ((uintptr_t)a.xdbl & 15) || ((uintptr_t)a.dxdbl & 7) || ((uintptr_t)a.ddelta & 15) || ((uintptr_t)a.part & 15)) {
+        set_error("dm_dtproj_bwd: xdbl rows must be 16-byte aligned (stride % 8), dxdbl rows 8-byte aligned (stride % 4)");
+        return DM_ERR_ARG;
+    }
+    return DM_OK;
+}
+static bool pairs_dtproj_bwd(const dm_dtproj_bwd_args& x, const dm_dtproj_bwd_args& y) {
+    return mix_congruent(x, y, &dm_dtproj_bwd_args::ddelta, &dm_dtproj_bwd_args::xdbl, &dm_dtproj_bwd_args::w, &dm_dtproj_bwd_args::dxdbl,
+                         &dm_dtproj_bwd_args::part);
+}
+static int run_dtproj_bwd(const dm_dtproj_bwd_args& a, const dm_dtproj_bwd_args* second, hipStream_t st) {
+    const int rc = (a.io_dtype == DM_BF16) ? dtproj_bwd_launch<bf16_t>(a, second, st) : dtproj_bwd_launch<f16_t>(a, second, st);
+    if (rc != DM_OK) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("dm_dtproj_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
+    return DM_OK;
+}
+
 }  // namespace dm
 
 extern "C" int dm_dtproj_bwd_supported(int dim, int rank, int io_dtype) {
@@ -376,39 +408,15 @@ extern "C" int dm_dtproj_bwd_supported(int dim, int rank, int io_dtype) {
 extern "C" int dm_dtproj_bwd(const dm_dtproj_bwd_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_dtproj_bwd: null args"); return DM_ERR_ARG; }
-    const dm_dtproj_bwd_args& a = *args;
-    if (!a.ddelta || !a.xdbl || !a.w || !a.dxdbl || !a.part) { set_error("dm_dtproj_bwd: null tensor pointer"); return DM_ERR_ARG; }
-    if (!dm_dtproj_bwd_supported(a.dim, a.rank, a.io_dtype)) { set_error("dm_dtproj_bwd: unsupported dim %d / rank %d / dtype %d", a.dim, a.rank, a.io_dtype); return DM_ERR_ARG; }
-    if (a.rows <= 0) { set_error("dm_dtproj_bwd: rows (%d) must be positive", a.rows); return DM_ERR_ARG; }
-    if (a.nblk <= 0 || a.nblk > (a.rows + DTB_TM - 1) / DTB_TM) { set_error("dm_dtproj_bwd: nblk (%d) must be in 1 .. ceil(rows / %d)", a.nblk, DTB_TM); return DM_ERR_ARG; }
-    if (a.xd_sr % 8 != 0 || a.dxd_sr % 4 != 0 || ((uintptr_t)a.xdbl & 15) || ((uintptr_t)a.dxdbl & 7) || ((uintptr_t)a.ddelta & 15) || ((uintptr_t)a.part & 15)) {
-        set_error("dm_dtproj_bwd: xdbl rows must be 16-byte aligned (stride % 8), dxdbl rows 8-byte aligned (stride % 4)");
-        return DM_ERR_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = (a.io_dtype == DM_BF16) ? dtproj_bwd_launch<bf16_t>(a, st) : dtproj_bwd_launch<f16_t>(a, st);
-    if (rc != DM_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_dtproj_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    const int rc = check_dtproj_bwd(*args);
+    return rc ? rc : run_dtproj_bwd(*args, nullptr, (hipStream_t)stream);
 }
 
-// ---- n congruent launches in one (the two mixers of a block at small batch; see dm_common.h mix_args) ------------------------
+// ---- n congruent launches in one (the two mixers of a block at small batch; see dm_common.h mix_run_n) -----------------------
+// One kernel instantiation per shape: congruence and each struct's own check are the whole pairing rule.
 extern "C" int dm_dtproj_softplus_fwd_n(const dm_dtproj_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_dtproj_softplus_fwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_dtproj_args* a) { return dm_dtproj_softplus_fwd(a, stream); },
-                        [](const dm_dtproj_args& x, const dm_dtproj_args& y) {
-                            return mix_congruent(x, y, &dm_dtproj_args::xdbl, &dm_dtproj_args::w, &dm_dtproj_args::bias, &dm_dtproj_args::delta);
-                        });
+    return dm::mix_run_n("dm_dtproj_softplus_fwd_n", args, n, stream, dm::check_dtproj_fwd, dm::pairs_dtproj_fwd, dm::run_dtproj_fwd);
 }
-
 extern "C" int dm_dtproj_bwd_n(const dm_dtproj_bwd_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_dtproj_bwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_dtproj_bwd_args* a) { return dm_dtproj_bwd(a, stream); },
-                        [](const dm_dtproj_bwd_args& x, const dm_dtproj_bwd_args& y) {
-                            return mix_congruent(x, y, &dm_dtproj_bwd_args::ddelta, &dm_dtproj_bwd_args::xdbl, &dm_dtproj_bwd_args::w,
-                                                 &dm_dtproj_bwd_args::dxdbl, &dm_dtproj_bwd_args::part);
-                        });
+    return dm::mix_run_n("dm_dtproj_bwd_n", args, n, stream, dm::check_dtproj_bwd, dm::pairs_dtproj_bwd, dm::run_dtproj_bwd);
 }

@@ -201,9 +201,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(const mix_args<dm_gemm_args> 
 }
 
 template <typename T, typename TC, int BM, int BN, int BK>
-static void gemm_launch_l(const dm_gemm_args& a, hipStream_t st) {
+static void gemm_launch_l(const dm_gemm_args& a, const dm_gemm_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_gemm_args> m = mix_make(a, gz);
+    const mix_args<dm_gemm_args> m = mix_make(a, second, gz);
     dim3 grid((a.Q + BN - 1) / BN, (a.P + BM - 1) / BM, gz), block(256);
     if (a.a_kmajor) {
         if (a.b_kmajor) hipLaunchKernelGGL((gemm_kernel<T, TC, BM, BN, BK, true, true>), grid, block, 0, st, m);
@@ -215,15 +215,43 @@ static void gemm_launch_l(const dm_gemm_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TC>
-static void gemm_launch_t(const dm_gemm_args& a, hipStream_t st) {
-    // Tile by the size of the grid (both mixers counted when a second struct is announced): the largest tile that still gives every CU
+static void gemm_launch_t(const dm_gemm_args& a, const dm_gemm_args* second, hipStream_t st) {
+    // Tile by the size of the grid (both mixers counted when a second struct rides along): the largest tile that still gives every CU
     // a workgroup -- these launches are bound by the L2 -> CU traffic of their operands (a 64 x 64 tile uses a loaded byte for 64
     // multiply-adds, a 128 x 128 tile for 128), not by the matrix pipe.  64 x 64 (BK 128) is the fallback for the smallest grids.
-    const int64_t n = mix_peek() ? 2 : 1;
+    const int64_t n = second ? 2 : 1;
     auto wgs = [&](int bm, int bn) { return n * (int64_t)((a.P + bm - 1) / bm) * ((a.Q + bn - 1) / bn); };
-    if (wgs(128, 128) >= 256) gemm_launch_l<T, TC, 128, 128, 64>(a, st);
-    else if (wgs(128, 64) >= 256) gemm_launch_l<T, TC, 128, 64, 64>(a, st);
-    else gemm_launch_l<T, TC, 64, 64, 128>(a, st);
+    if (wgs(128, 128) >= 256) gemm_launch_l<T, TC, 128, 128, 64>(a, second, st);
+    else if (wgs(128, 64) >= 256) gemm_launch_l<T, TC, 128, 64, 64>(a, second, st);
+    else gemm_launch_l<T, TC, 64, 64, 128>(a, second, st);
+}
+
+static int check_gemm(const dm_gemm_args& a) {
+    if (!a.a || !a.b || !a.c) { set_error("dm_gemm: null tensor pointer"); return DM_ERR_ARG; }
+    if (!dm_gemm_supported(a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype)) {
+        set_error("dm_gemm: unsupported shape / dtype (P %d Q %d Kc %d, a_kmajor %d b_kmajor %d, dtypes %d -> %d): 16-bit operands, "
+                  "Q %% 8 == 0, and the contiguous index of every operand a multiple of 8", a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype);
+        return DM_ERR_ARG;
+    }
+    const int64_t a_min = a.a_kmajor ? a.Kc : a.P, b_min = a.b_kmajor ? a.Kc : a.Q;
+    if (a.lda < a_min || a.ldb < b_min || a.ldc < a.Q || a.lda % 8 || a.ldb % 8 || a.ldc % 4 ||
+        ((uintptr_t)a.a % 16) || ((uintptr_t)a.b % 16) || ((uintptr_t)a.c % 16)) {
+        set_error("dm_gemm: row strides must cover a row, be multiples of 8 (operands) / 4 (C) elements, and the tensors 16-byte aligned");
+        return DM_ERR_LAYOUT;
+    }
+    if ((a.P + 63) / 64 > 65535) { set_error("dm_gemm: P too large"); return DM_ERR_ARG; }
+    return DM_OK;
+}
+static bool pairs_gemm(const dm_gemm_args& x, const dm_gemm_args& y) {
+    return mix_congruent(x, y, &dm_gemm_args::a, &dm_gemm_args::b, &dm_gemm_args::c);       // check leaves no alignment to compare
+}
+static int run_gemm(const dm_gemm_args& a, const dm_gemm_args* second, hipStream_t st) {
+    const bool c32 = a.c_dtype == DM_F32;
+    if (a.ab_dtype == DM_BF16) { if (c32) gemm_launch_t<bf16_t, float>(a, second, st); else gemm_launch_t<bf16_t, bf16_t>(a, second, st); }
+    else { if (c32) gemm_launch_t<f16_t, float>(a, second, st); else gemm_launch_t<f16_t, f16_t>(a, second, st); }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("dm_gemm: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
+    return DM_OK;
 }
 
 }  // namespace dm
@@ -239,37 +267,10 @@ extern "C" int dm_gemm_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajo
 extern "C" int dm_gemm(const dm_gemm_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_gemm: null args"); return DM_ERR_ARG; }
-    const dm_gemm_args& a = *args;
-    if (!a.a || !a.b || !a.c) { set_error("dm_gemm: null tensor pointer"); return DM_ERR_ARG; }
-    if (!dm_gemm_supported(a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype)) {
-        set_error("dm_gemm: unsupported shape / dtype (P %d Q %d Kc %d, a_kmajor %d b_kmajor %d, dtypes %d -> %d): 16-bit operands, "
-                  "Q %% 8 == 0, and the contiguous index of every operand a multiple of 8", a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype);
-        return DM_ERR_ARG;
-    }
-    const int64_t a_min = a.a_kmajor ? a.Kc : a.P, b_min = a.b_kmajor ? a.Kc : a.Q;
-    if (a.lda < a_min || a.ldb < b_min || a.ldc < a.Q || a.lda % 8 || a.ldb % 8 || a.ldc % 4 ||
-        ((uintptr_t)a.a % 16) || ((uintptr_t)a.b % 16) || ((uintptr_t)a.c % 16)) {
-        set_error("dm_gemm: row strides must cover a row, be multiples of 8 (operands) / 4 (C) elements, and the tensors 16-byte aligned");
-        return DM_ERR_LAYOUT;
-    }
-    if ((a.P + 63) / 64 > 65535) { set_error("dm_gemm: P too large"); return DM_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    const bool c32 = a.c_dtype == DM_F32;
-    if (a.ab_dtype == DM_BF16) { if (c32) gemm_launch_t<bf16_t, float>(a, st); else gemm_launch_t<bf16_t, bf16_t>(a, st); }
-    else { if (c32) gemm_launch_t<f16_t, float>(a, st); else gemm_launch_t<f16_t, f16_t>(a, st); }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gemm: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    const int rc = check_gemm(*args);
+    return rc ? rc : run_gemm(*args, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int dm_gemm_n(const dm_gemm_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_gemm_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_gemm_args* a) { return dm_gemm(a, stream); },
-                        [](const dm_gemm_args& x, const dm_gemm_args& y) {
-                            // dm_gemm validates args[i] only: a second struct rides along only with the same 16-byte alignment
-                            auto al = [](const void* p, const void* q) { return (((uintptr_t)p ^ (uintptr_t)q) & 15) == 0; };
-                            return al(x.a, y.a) && al(x.b, y.b) && al(x.c, y.c) &&
-                                   mix_congruent(x, y, &dm_gemm_args::a, &dm_gemm_args::b, &dm_gemm_args::c);
-                        });
+    return dm::mix_run_n("dm_gemm_n", args, n, stream, dm::check_gemm, dm::pairs_gemm, dm::run_gemm);
 }

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const mix_args<dm_merge_args
 }
 
 template <typename TI, typename TO>
-static int launch_merge(const dm_merge_args& a, hipStream_t st) {
+static int launch_merge(const dm_merge_args& a, const dm_merge_args* second, hipStream_t st) {
     constexpr int VECMAX = 16 / sizeof(TI);
     bool vec_ok = (a.dim % VECMAX == 0) && (a.in_sk % VECMAX == 0) && (a.in_sb % VECMAX == 0) &&
                   (a.in_sl % VECMAX == 0) && (a.o_sb % VECMAX == 0) && (a.o_sl % VECMAX == 0) &&
@@ -95,7 +95,7 @@ static int launch_merge(const dm_merge_args& a, hipStream_t st) {
     if (a.gate) vec_ok = vec_ok && (a.g_sb % VECMAX == 0) && (a.g_sl % VECMAX == 0) && (((uintptr_t)a.gate) % 16 == 0);
     if (a.pre) vec_ok = vec_ok && (a.p_sb % VECMAX == 0) && (a.p_sl % VECMAX == 0) && (((uintptr_t)a.pre) % 16 == 0);
     unsigned gz;
-    const mix_args<dm_merge_args> m = mix_make(a, gz);
+    const mix_args<dm_merge_args> m = mix_make(a, second, gz);
     if (vec_ok) {
         dim3 grid((a.dim / VECMAX + 255) / 256, a.seqlen, a.batch * gz);
         if (a.gate) hipLaunchKernelGGL((merge_kernel<TI, TO, VECMAX, true>), grid, dim3(256), 0, st, m);
@@ -110,25 +110,36 @@ static int launch_merge(const dm_merge_args& a, hipStream_t st) {
     return DM_OK;
 }
 
-}  // namespace dm
-
-extern "C" int dm_token_merge(const dm_merge_args* args, void* stream) {
-    using namespace dm;
-    if (!args) { set_error("dm_token_merge: null args"); return DM_ERR_ARG; }
-    const dm_merge_args& a = *args;
+static int check_merge(const dm_merge_args& a) {
     if (!a.in || !a.out) { set_error("dm_token_merge: null tensor pointer"); return DM_ERR_ARG; }
     if (a.nin <= 0 || a.batch <= 0 || a.seqlen <= 0 || a.dim <= 0) { set_error("dm_token_merge: non-positive size"); return DM_ERR_ARG; }
     if (a.batch * DM_MAX_MIX > 65535 || a.seqlen > 65535) { set_error("dm_token_merge: batch > 32767 or seqlen > 65535"); return DM_ERR_ARG; }
     if (a.pre && !a.gate) { set_error("dm_token_merge: pre is only written by the gated form (gate != NULL)"); return DM_ERR_ARG; }
     if (a.gate && a.io_dtype != a.out_dtype) { set_error("dm_token_merge: the gated form keeps one dtype (in, gate, pre, out)"); return DM_ERR_DTYPE; }
-    hipStream_t st = (hipStream_t)stream;
-    if (a.io_dtype == DM_F32 && a.out_dtype == DM_F32) return launch_merge<float, float>(a, st);
-    if (a.io_dtype == DM_BF16 && a.out_dtype == DM_BF16) return launch_merge<bf16_t, bf16_t>(a, st);
-    if (a.io_dtype == DM_F16 && a.out_dtype == DM_F16) return launch_merge<f16_t, f16_t>(a, st);
-    if (a.io_dtype == DM_F32 && a.out_dtype == DM_BF16) return launch_merge<float, bf16_t>(a, st);
-    if (a.io_dtype == DM_F32 && a.out_dtype == DM_F16) return launch_merge<float, f16_t>(a, st);
+    return DM_OK;
+}
+static bool pairs_merge(const dm_merge_args& x, const dm_merge_args& y) {
+    return same_align16(x.in, y.in) && same_align16(x.out, y.out) && same_align16(x.gate, y.gate) &&
+           same_align16(x.pre, y.pre) &&          // the 16-byte form is chosen per pointer
+           mix_congruent(x, y, &dm_merge_args::in, &dm_merge_args::row_index, &dm_merge_args::out, &dm_merge_args::gate, &dm_merge_args::pre);
+}
+static int run_merge(const dm_merge_args& a, const dm_merge_args* second, hipStream_t st) {
+    if (a.io_dtype == DM_F32 && a.out_dtype == DM_F32) return launch_merge<float, float>(a, second, st);
+    if (a.io_dtype == DM_BF16 && a.out_dtype == DM_BF16) return launch_merge<bf16_t, bf16_t>(a, second, st);
+    if (a.io_dtype == DM_F16 && a.out_dtype == DM_F16) return launch_merge<f16_t, f16_t>(a, second, st);
+    if (a.io_dtype == DM_F32 && a.out_dtype == DM_BF16) return launch_merge<float, bf16_t>(a, second, st);
+    if (a.io_dtype == DM_F32 && a.out_dtype == DM_F16) return launch_merge<float, f16_t>(a, second, st);
     set_error("dm_token_merge: unsupported dtype pair (%d -> %d)", a.io_dtype, a.out_dtype);
     return DM_ERR_DTYPE;
+}
+
+}  // namespace dm
+
+extern "C" int dm_token_merge(const dm_merge_args* args, void* stream) {
+    using namespace dm;
+    if (!args) { set_error("dm_token_merge: null args"); return DM_ERR_ARG; }
+    const int rc = check_merge(*args);
+    return rc ? rc : run_merge(*args, nullptr, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -162,13 +173,13 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const mix_args<dm_gate_bw
 }
 
 template <typename T>
-static int launch_gate_bwd(const dm_gate_bwd_args& a, hipStream_t st) {
+static int launch_gate_bwd(const dm_gate_bwd_args& a, const dm_gate_bwd_args* second, hipStream_t st) {
     constexpr int VECMAX = 16 / sizeof(T);
     auto al = [&](const void* ptr, int64_t sb, int64_t sl) { return (uintptr_t)ptr % 16 == 0 && sb % VECMAX == 0 && sl % VECMAX == 0; };
     const bool vec_ok = a.dim % VECMAX == 0 && al(a.dy, a.dy_sb, a.dy_sl) && al(a.z, a.z_sb, a.z_sl) && al(a.pre, a.p_sb, a.p_sl) &&
                         al(a.g, a.g_sb, a.g_sl) && al(a.dz, a.dz_sb, a.dz_sl);
     unsigned gz;
-    const mix_args<dm_gate_bwd_args> m = mix_make(a, gz);
+    const mix_args<dm_gate_bwd_args> m = mix_make(a, second, gz);
     if (vec_ok) {
         dim3 grid((a.dim / VECMAX + 255) / 256, a.seqlen, a.batch * gz);
         hipLaunchKernelGGL((gate_bwd_kernel<T, VECMAX>), grid, dim3(256), 0, st, m);
@@ -180,22 +191,33 @@ static int launch_gate_bwd(const dm_gate_bwd_args& a, hipStream_t st) {
     if (e != hipSuccess) { set_error("dm_gate_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
     return DM_OK;
 }
+
+static int check_gate_bwd(const dm_gate_bwd_args& a) {
+    if (!a.dy || !a.z || !a.pre || !a.g || !a.dz) { set_error("dm_gate_bwd: null tensor pointer"); return DM_ERR_ARG; }
+    if (a.batch <= 0 || a.seqlen <= 0 || a.dim <= 0) { set_error("dm_gate_bwd: non-positive size"); return DM_ERR_ARG; }
+    if (a.batch * DM_MAX_MIX > 65535 || a.seqlen > 65535) { set_error("dm_gate_bwd: batch > 32767 or seqlen > 65535"); return DM_ERR_ARG; }
+    return DM_OK;
+}
+static bool pairs_gate_bwd(const dm_gate_bwd_args& x, const dm_gate_bwd_args& y) {
+    return same_align16(x.dy, y.dy) && same_align16(x.z, y.z) && same_align16(x.pre, y.pre) && same_align16(x.g, y.g) &&
+           same_align16(x.dz, y.dz) &&            // the 16-byte form is chosen per pointer
+           mix_congruent(x, y, &dm_gate_bwd_args::dy, &dm_gate_bwd_args::z, &dm_gate_bwd_args::pre, &dm_gate_bwd_args::g, &dm_gate_bwd_args::dz);
+}
+static int run_gate_bwd(const dm_gate_bwd_args& a, const dm_gate_bwd_args* second, hipStream_t st) {
+    switch (a.io_dtype) {
+        case DM_F32: return launch_gate_bwd<float>(a, second, st);
+        case DM_BF16: return launch_gate_bwd<bf16_t>(a, second, st);
+        case DM_F16: return launch_gate_bwd<f16_t>(a, second, st);
+        default: set_error("dm_gate_bwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
+    }
+}
 }  // namespace dm
 
 extern "C" int dm_gate_bwd(const dm_gate_bwd_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_gate_bwd: null args"); return DM_ERR_ARG; }
-    const dm_gate_bwd_args& a = *args;
-    if (!a.dy || !a.z || !a.pre || !a.g || !a.dz) { set_error("dm_gate_bwd: null tensor pointer"); return DM_ERR_ARG; }
-    if (a.batch <= 0 || a.seqlen <= 0 || a.dim <= 0) { set_error("dm_gate_bwd: non-positive size"); return DM_ERR_ARG; }
-    if (a.batch * DM_MAX_MIX > 65535 || a.seqlen > 65535) { set_error("dm_gate_bwd: batch > 32767 or seqlen > 65535"); return DM_ERR_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    switch (a.io_dtype) {
-        case DM_F32: return launch_gate_bwd<float>(a, st);
-        case DM_BF16: return launch_gate_bwd<bf16_t>(a, st);
-        case DM_F16: return launch_gate_bwd<f16_t>(a, st);
-        default: set_error("dm_gate_bwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
-    }
+    const int rc = check_gate_bwd(*args);
+    return rc ? rc : run_gate_bwd(*args, nullptr, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -235,26 +257,34 @@ __global__ __launch_bounds__(64 * CS_WAVES) void colsum_kernel(const mix_args<dm
         *reinterpret_cast<f32x4*>(out + c) = t;
     }
 }
+
+static int check_colsum(const dm_colsum_args& a) {
+    if (!a.in || !a.out) { set_error("dm_colsum_f32: null tensor pointer"); return DM_ERR_ARG; }
+    if (a.rows <= 0 || a.cols <= 0 || a.cols % 4 != 0 || a.rows > 0x7fffffff || a.cols > 0x7fffffff) {
+        set_error("dm_colsum_f32: rows, cols must be positive and cols a multiple of 4"); return DM_ERR_ARG;
+    }
+    if (((uintptr_t)a.in % 16) || ((uintptr_t)a.out % 16)) { set_error("dm_colsum_f32: tensors must be 16-byte aligned"); return DM_ERR_LAYOUT; }
+    return DM_OK;
+}
+static bool pairs_colsum(const dm_colsum_args& x, const dm_colsum_args& y) {
+    return mix_congruent(x, y, &dm_colsum_args::in, &dm_colsum_args::out);       // one instantiation: check leaves no alignment to compare
+}
+static int run_colsum(const dm_colsum_args& a, const dm_colsum_args* second, hipStream_t st) {
+    unsigned gz;
+    const mix_args<dm_colsum_args> m = mix_make(a, second, gz);
+    dim3 grid((unsigned)((a.cols / 4 + WAVE - 1) / WAVE), 1, gz);
+    hipLaunchKernelGGL(colsum_kernel, grid, dim3(64 * CS_WAVES), 0, st, m);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("dm_colsum_f32: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
+    return DM_OK;
+}
 }  // namespace dm
 
 extern "C" int dm_colsum_f32(const dm_colsum_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_colsum_f32: null args"); return DM_ERR_ARG; }
-    const float* in = args->in;
-    float* out = args->out;
-    const int64_t rows = args->rows, cols = args->cols;
-    if (!in || !out) { set_error("dm_colsum_f32: null tensor pointer"); return DM_ERR_ARG; }
-    if (rows <= 0 || cols <= 0 || cols % 4 != 0 || rows > 0x7fffffff || cols > 0x7fffffff) {
-        set_error("dm_colsum_f32: rows, cols must be positive and cols a multiple of 4"); return DM_ERR_ARG;
-    }
-    if (((uintptr_t)in % 16) || ((uintptr_t)out % 16)) { set_error("dm_colsum_f32: tensors must be 16-byte aligned"); return DM_ERR_LAYOUT; }
-    unsigned gz;
-    const mix_args<dm_colsum_args> m = mix_make(*args, gz);
-    dim3 grid((unsigned)((cols / 4 + WAVE - 1) / WAVE), 1, gz);
-    hipLaunchKernelGGL(colsum_kernel, grid, dim3(64 * CS_WAVES), 0, (hipStream_t)stream, m);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_colsum_f32: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    const int rc = check_colsum(*args);
+    return rc ? rc : run_colsum(*args, nullptr, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -279,22 +309,23 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const mix_args<dm_sum
     if constexpr (sizeof(TO) == 2) *reinterpret_cast<f32x2*>(dst) = *reinterpret_cast<const f32x2*>(o);
     else *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(o);
 }
-}  // namespace dm
 
-extern "C" int dm_sum_partials(const dm_sum_partials_args* args, void* stream) {
-    using namespace dm;
-    if (!args) { set_error("dm_sum_partials: null args"); return DM_ERR_ARG; }
-    const dm_sum_partials_args& a = *args;
+static int check_sum_partials(const dm_sum_partials_args& a) {
     if (!a.in || !a.out) { set_error("dm_sum_partials: null tensor pointer"); return DM_ERR_ARG; }
     if (a.rows <= 0 || a.nw <= 0 || a.cols <= 0 || a.cols % 4 != 0) { set_error("dm_sum_partials: rows, nw, cols must be positive and cols a multiple of 4"); return DM_ERR_ARG; }
     const int es = a.out_dtype == DM_F32 ? 4 : 2;
     if (((uintptr_t)a.in % 16) || ((uintptr_t)a.out % (4 * es)) || (a.out_sr % 4)) { set_error("dm_sum_partials: in must be 16-byte aligned, out rows aligned to 4 elements"); return DM_ERR_LAYOUT; }
-    const int64_t n = a.rows * (a.cols / 4);
-    if ((n + 255) / 256 > 0x7fffffff) { set_error("dm_sum_partials: too many rows"); return DM_ERR_ARG; }
+    if ((a.rows * (a.cols / 4) + 255) / 256 > 0x7fffffff) { set_error("dm_sum_partials: too many rows"); return DM_ERR_ARG; }
+    return DM_OK;
+}
+static bool pairs_sum_partials(const dm_sum_partials_args& x, const dm_sum_partials_args& y) {
+    // a 16-bit out may be 8- or 16-byte aligned: such a pair stays apart
+    return same_align16(x.out, y.out) && mix_congruent(x, y, &dm_sum_partials_args::in, &dm_sum_partials_args::out);
+}
+static int run_sum_partials(const dm_sum_partials_args& a, const dm_sum_partials_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_sum_partials_args> m = mix_make(a, gz);
-    dim3 grid((unsigned)((n + 255) / 256), 1, gz);
-    hipStream_t st = (hipStream_t)stream;
+    const mix_args<dm_sum_partials_args> m = mix_make(a, second, gz);
+    dim3 grid((unsigned)((a.rows * (a.cols / 4) + 255) / 256), 1, gz);
     switch (a.out_dtype) {
         case DM_F32: hipLaunchKernelGGL((sum_partials_kernel<float>), grid, dim3(256), 0, st, m); break;
         case DM_BF16: hipLaunchKernelGGL((sum_partials_kernel<bf16_t>), grid, dim3(256), 0, st, m); break;
@@ -305,51 +336,25 @@ extern "C" int dm_sum_partials(const dm_sum_partials_args* args, void* stream) {
     if (e != hipSuccess) { set_error("dm_sum_partials: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
     return DM_OK;
 }
+}  // namespace dm
 
-// ---- n congruent launches in one (the two mixers of a block at small batch; see dm_common.h mix_args) ------------------------
-static inline bool same_align16(const void* x, const void* y) { return (((uintptr_t)x ^ (uintptr_t)y) & 15) == 0; }
+extern "C" int dm_sum_partials(const dm_sum_partials_args* args, void* stream) {
+    using namespace dm;
+    if (!args) { set_error("dm_sum_partials: null args"); return DM_ERR_ARG; }
+    const int rc = check_sum_partials(*args);
+    return rc ? rc : run_sum_partials(*args, nullptr, (hipStream_t)stream);
+}
 
+// ---- n congruent launches in one (the two mixers of a block at small batch; see dm_common.h mix_run_n) -----------------------
 extern "C" int dm_token_merge_n(const dm_merge_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_token_merge_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_merge_args* a) { return dm_token_merge(a, stream); },
-                        [](const dm_merge_args& x, const dm_merge_args& y) {
-                            return same_align16(x.in, y.in) && same_align16(x.out, y.out) && same_align16(x.gate, y.gate) &&
-                                   same_align16(x.pre, y.pre) &&          // the 16-byte form is chosen per pointer
-                                   mix_congruent(x, y, &dm_merge_args::in, &dm_merge_args::row_index, &dm_merge_args::out,
-                                                 &dm_merge_args::gate, &dm_merge_args::pre);
-                        });
+    return dm::mix_run_n("dm_token_merge_n", args, n, stream, dm::check_merge, dm::pairs_merge, dm::run_merge);
 }
-
 extern "C" int dm_gate_bwd_n(const dm_gate_bwd_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_gate_bwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_gate_bwd_args* a) { return dm_gate_bwd(a, stream); },
-                        [](const dm_gate_bwd_args& x, const dm_gate_bwd_args& y) {
-                            return same_align16(x.dy, y.dy) && same_align16(x.z, y.z) && same_align16(x.pre, y.pre) &&
-                                   same_align16(x.g, y.g) && same_align16(x.dz, y.dz) &&
-                                   mix_congruent(x, y, &dm_gate_bwd_args::dy, &dm_gate_bwd_args::z, &dm_gate_bwd_args::pre,
-                                                 &dm_gate_bwd_args::g, &dm_gate_bwd_args::dz);
-                        });
+    return dm::mix_run_n("dm_gate_bwd_n", args, n, stream, dm::check_gate_bwd, dm::pairs_gate_bwd, dm::run_gate_bwd);
 }
-
 extern "C" int dm_colsum_f32_n(const dm_colsum_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_colsum_f32_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_colsum_args* a) { return dm_colsum_f32(a, stream); },
-                        [](const dm_colsum_args& x, const dm_colsum_args& y) {
-                            // the single entry validates args[i] only: the second struct must have the alignment of the first
-                            return same_align16(x.in, y.in) && same_align16(x.out, y.out) &&
-                                   mix_congruent(x, y, &dm_colsum_args::in, &dm_colsum_args::out);
-                        });
+    return dm::mix_run_n("dm_colsum_f32_n", args, n, stream, dm::check_colsum, dm::pairs_colsum, dm::run_colsum);
 }
-
 extern "C" int dm_sum_partials_n(const dm_sum_partials_args* args, int n, void* stream) {
-    using namespace dm;
-    if (!args || n <= 0) { set_error("dm_sum_partials_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_sum_partials_args* a) { return dm_sum_partials(a, stream); },
-                        [](const dm_sum_partials_args& x, const dm_sum_partials_args& y) {
-                            return same_align16(x.in, y.in) && same_align16(x.out, y.out) &&
-                                   mix_congruent(x, y, &dm_sum_partials_args::in, &dm_sum_partials_args::out);
-                        });
+    return dm::mix_run_n("dm_sum_partials_n", args, n, stream, dm::check_sum_partials, dm::pairs_sum_partials, dm::run_sum_partials);
 }

@@ -2,15 +2,12 @@
 #include "dm_common.h"
 namespace dm {
 constexpr int BWD_SUB = 4;     // = checkpoint spacing (scan_bwd_impl.h)
-int scan_bwd_f32(const dm_scan_bwd_args& a, hipStream_t st);
-int scan_bwd_bf16(const dm_scan_bwd_args& a, hipStream_t st);
-int scan_bwd_f16(const dm_scan_bwd_args& a, hipStream_t st);
-}  // namespace dm
+int scan_bwd_f32(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
+int scan_bwd_bf16(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
+int scan_bwd_f16(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
+bool scan_bwd_takes_two(const dm_scan_bwd_args& a);      // the kernel selection of bwd_dispatch (scan_bwd_chunked.h)
 
-extern "C" int dm_selective_scan_bwd(const dm_scan_bwd_args* args, void* stream) {
-    using namespace dm;
-    if (!args) { set_error("dm_selective_scan_bwd: null args"); return DM_ERR_ARG; }
-    const dm_scan_bwd_args& a = *args;
+static int check_scan_bwd(const dm_scan_bwd_args& a) {
     if (!a.u || !a.delta || !a.dout || !a.A || !a.B || !a.C || !a.du || !a.ddelta || !a.dBC_partial || !a.dA_partial) {
         set_error("dm_selective_scan_bwd: null tensor pointer"); return DM_ERR_ARG;
     }
@@ -37,24 +34,32 @@ extern "C" int dm_selective_scan_bwd(const dm_scan_bwd_args* args, void* stream)
     if ((a.z_row_index == nullptr) != (a.out_row_index == nullptr)) {
         set_error("dm_selective_scan_bwd: z_row_index and out_row_index must both be set or both be NULL"); return DM_ERR_ARG;
     }
-    hipStream_t st = (hipStream_t)stream;
+    return DM_OK;
+}
+// two structs share a launch when the shape selects the small-launch (chunk-parallel) kernel (dm_common.h mix_args)
+static bool pairs_scan_bwd(const dm_scan_bwd_args& x, const dm_scan_bwd_args& y) {
+    using A = dm_scan_bwd_args;
+    return scan_bwd_takes_two(x) && mix_congruent(x, y, &A::u, &A::delta, &A::z, &A::dout, &A::B, &A::C, &A::A, &A::D, &A::delta_bias,
+                                                  &A::z_row_index, &A::out_row_index, &A::ckpt, &A::du, &A::ddelta, &A::dz,
+                                                  &A::dBC_partial, &A::dA_partial, &A::dD_partial, &A::dbias_partial);
+}
+static int run_scan_bwd(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st) {
     switch (a.io_dtype) {
-        case DM_F32: return scan_bwd_f32(a, st);
-        case DM_BF16: return scan_bwd_bf16(a, st);
-        case DM_F16: return scan_bwd_f16(a, st);
+        case DM_F32: return scan_bwd_f32(a, second, st);
+        case DM_BF16: return scan_bwd_bf16(a, second, st);
+        case DM_F16: return scan_bwd_f16(a, second, st);
         default: set_error("dm_selective_scan_bwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
     }
 }
+}  // namespace dm
 
-// n congruent launches in one when the shape selects the small-launch (chunk-parallel) kernel (dm_common.h mix_args)
-extern "C" int dm_selective_scan_bwd_n(const dm_scan_bwd_args* args, int n, void* stream) {
+extern "C" int dm_selective_scan_bwd(const dm_scan_bwd_args* args, void* stream) {
     using namespace dm;
-    if (!args || n <= 0) { set_error("dm_selective_scan_bwd_n: null args / n <= 0"); return DM_ERR_ARG; }
-    return mix_launch_n(args, n, [&](const dm_scan_bwd_args* a) { return dm_selective_scan_bwd(a, stream); },
-                        [](const dm_scan_bwd_args& x, const dm_scan_bwd_args& y) {
-                            using A = dm_scan_bwd_args;
-                            return mix_congruent(x, y, &A::u, &A::delta, &A::z, &A::dout, &A::B, &A::C, &A::A, &A::D, &A::delta_bias,
-                                                 &A::z_row_index, &A::out_row_index, &A::ckpt, &A::du, &A::ddelta, &A::dz,
-                                                 &A::dBC_partial, &A::dA_partial, &A::dD_partial, &A::dbias_partial);
-                        });
+    if (!args) { set_error("dm_selective_scan_bwd: null args"); return DM_ERR_ARG; }
+    const int rc = check_scan_bwd(*args);
+    return rc ? rc : run_scan_bwd(*args, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int dm_selective_scan_bwd_n(const dm_scan_bwd_args* args, int n, void* stream) {
+    return dm::mix_run_n("dm_selective_scan_bwd_n", args, n, stream, dm::check_scan_bwd, dm::pairs_scan_bwd, dm::run_scan_bwd);
 }

@@ -388,11 +388,16 @@ static inline int bwd_chunked_lc(int nseq, int dim, int seqlen, int dstate, int 
     if (seqlen > 2 * BWD_CHUNKED_LC_SHORT && seqlen <= BWD_CHUNKED_NW * BWD_CHUNKED_LC_SHORT) return BWD_CHUNKED_LC_SHORT;
     return 0;
 }
+// steps per chunk if the launch goes to this family -- the one backward scan that takes two argument structs (bwd_dispatch, and
+// the pairing rule of dm_selective_scan_bwd_n through scan_bwd_takes_two) -- else 0
+static inline int bwd_goes_chunked(const dm_scan_bwd_args& a) {
+    return (a.bc_dtype == DM_F32 || a.bc_dtype == a.io_dtype) ? bwd_chunked_lc(a.nseq, a.dim, a.seqlen, a.dstate, a.flags) : 0;
+}
 
 template <typename T, typename TBC, bool HAS_Z, bool IDX, int LC>
-static void launch_bwd_chunked3(const dm_scan_bwd_args& a, hipStream_t st) {
+static void launch_bwd_chunked3(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_scan_bwd_args> m = mix_make(a, gz);
+    const mix_args<dm_scan_bwd_args> m = mix_make(a, second, gz);
     dim3 grid((a.dim + WAVE - 1) / WAVE, a.nseq, gz), block(WAVE * BWD_CHUNKED_NW);
     const bool sp = (a.flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
     if constexpr (HAS_Z && IDX) {
@@ -412,12 +417,12 @@ static void launch_bwd_chunked3(const dm_scan_bwd_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TBC>
-static int launch_bwd_chunked(const dm_scan_bwd_args& a, hipStream_t st, int lc) {
+static int launch_bwd_chunked(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st, int lc) {
     const bool idx = a.z_row_index != nullptr;
 #define DM_BWDC(HZ, IX)                                                                       \
     do {                                                                                      \
-        if (lc == BWD_CHUNKED_LC_LONG) launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_LONG>(a, st); \
-        else launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_SHORT>(a, st);                  \
+        if (lc == BWD_CHUNKED_LC_LONG) launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_LONG>(a, second, st); \
+        else launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_SHORT>(a, second, st);          \
     } while (0)
     if (a.z) {
         if (idx) DM_BWDC(true, true);
@@ -433,12 +438,10 @@ static int launch_bwd_chunked(const dm_scan_bwd_args& a, hipStream_t st, int lc)
 }
 
 template <typename T>
-static int bwd_dispatch(const dm_scan_bwd_args& a, hipStream_t st) {
-    const int lc = bwd_chunked_lc(a.nseq, a.dim, a.seqlen, a.dstate, a.flags);
-    if (lc > 0) {
-        if (a.bc_dtype == DM_F32) return launch_bwd_chunked<T, float>(a, st, lc);
-        if (a.bc_dtype == a.io_dtype) return launch_bwd_chunked<T, T>(a, st, lc);
-    }
+static int bwd_dispatch(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st) {
+    const int lc = bwd_goes_chunked(a);
+    if (lc > 0) return a.bc_dtype == DM_F32 ? launch_bwd_chunked<T, float>(a, second, st, lc) : launch_bwd_chunked<T, T>(a, second, st, lc);
+    if (second) { set_error("dm_selective_scan_bwd: the sequential kernel takes one argument struct"); return DM_ERR_ARG; }
     return bwd_dispatch_bc<T>(a, st);
 }
 

@@ -1,7 +1,8 @@
 // scan_bwd: f32 I/O instantiations (split per dtype so the library builds in parallel)
 #include "scan_bwd_chunked.h"
 namespace dm {
-int scan_bwd_f32(const dm_scan_bwd_args& a, hipStream_t st) { return bwd_dispatch<float>(a, st); }
+int scan_bwd_f32(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st) { return bwd_dispatch<float>(a, second, st); }
+bool scan_bwd_takes_two(const dm_scan_bwd_args& a) { return bwd_goes_chunked(a) > 0; }
 }  // namespace dm
 
 extern "C" int dm_scan_bwd_group_channels(int dstate) {

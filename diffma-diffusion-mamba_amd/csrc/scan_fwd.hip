@@ -2,11 +2,12 @@
 #include "dm_common.h"
 namespace dm {
 constexpr int FWD_CKE = 4;      // checkpoint spacing (scan_fwd_impl.h)
-int scan_fwd_f32(const dm_scan_fwd_args& a, hipStream_t st);
-int scan_fwd_bf16(const dm_scan_fwd_args& a, hipStream_t st);
-int scan_fwd_f16(const dm_scan_fwd_args& a, hipStream_t st);
-}  // namespace dm
+int scan_fwd_f32(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
+int scan_fwd_bf16(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
+int scan_fwd_f16(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
+bool scan_fwd_takes_two(const dm_scan_fwd_args& a);      // the kernel selection of dispatch_fwd (scan_fwd_chunked.h)
 
+// check / pairs / run see NORMALISED structs only (both entry points normalise first)
 static dm_scan_fwd_args scan_fwd_normalised(dm_scan_fwd_args a) {
     if (a.flags & DM_FLAG_DELTA_ACTIVATED) {          // delta already holds softplus(raw + bias): the forward uses it as is
         a.flags &= ~(DM_FLAG_DELTA_ACTIVATED | DM_FLAG_DELTA_SOFTPLUS);
@@ -15,10 +16,7 @@ static dm_scan_fwd_args scan_fwd_normalised(dm_scan_fwd_args a) {
     return a;
 }
 
-extern "C" int dm_selective_scan_fwd(const dm_scan_fwd_args* args, void* stream) {
-    using namespace dm;
-    if (!args) { set_error("dm_selective_scan_fwd: null args"); return DM_ERR_ARG; }
-    const dm_scan_fwd_args a = scan_fwd_normalised(*args);
+static int check_scan_fwd(const dm_scan_fwd_args& a) {
     if (!a.u || !a.delta || !a.out || !a.A || !a.B || !a.C) {
         set_error("dm_selective_scan_fwd: null tensor pointer"); return DM_ERR_ARG;
     }
@@ -52,26 +50,37 @@ extern "C" int dm_selective_scan_fwd(const dm_scan_fwd_args* args, void* stream)
             return DM_ERR_ARG;
         }
     }
-    hipStream_t st = (hipStream_t)stream;
+    return DM_OK;
+}
+// two structs share a launch when the shape selects the small-launch (chunk-parallel) kernel, which takes an array of argument
+// structs (dm_common.h mix_args); the sequential kernel runs them one after the other.
+static bool pairs_scan_fwd(const dm_scan_fwd_args& x, const dm_scan_fwd_args& y) {
+    using A = dm_scan_fwd_args;
+    return scan_fwd_takes_two(x) && mix_congruent(x, y, &A::u, &A::delta, &A::z, &A::out, &A::B, &A::C, &A::A, &A::D, &A::delta_bias,
+                                                  &A::z_row_index, &A::out_row_index, &A::ckpt, &A::last_state);
+}
+static int run_scan_fwd(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st) {
     switch (a.io_dtype) {
-        case DM_F32: return scan_fwd_f32(a, st);
-        case DM_BF16: return scan_fwd_bf16(a, st);
-        case DM_F16: return scan_fwd_f16(a, st);
+        case DM_F32: return scan_fwd_f32(a, second, st);
+        case DM_BF16: return scan_fwd_bf16(a, second, st);
+        case DM_F16: return scan_fwd_f16(a, second, st);
         default: set_error("dm_selective_scan_fwd: bad io_dtype %d", a.io_dtype); return DM_ERR_DTYPE;
     }
 }
+}  // namespace dm
 
-// n congruent launches in one when the shape selects the small-launch (chunk-parallel) kernel, which takes an array of argument
-// structs (dm_common.h mix_args); the sequential kernel runs them one after the other.
+extern "C" int dm_selective_scan_fwd(const dm_scan_fwd_args* args, void* stream) {
+    using namespace dm;
+    if (!args) { set_error("dm_selective_scan_fwd: null args"); return DM_ERR_ARG; }
+    const dm_scan_fwd_args a = scan_fwd_normalised(*args);
+    const int rc = check_scan_fwd(a);
+    return rc ? rc : run_scan_fwd(a, nullptr, (hipStream_t)stream);
+}
+
 extern "C" int dm_selective_scan_fwd_n(const dm_scan_fwd_args* args, int n, void* stream) {
     using namespace dm;
     if (!args || n <= 0 || n > 16) { set_error("dm_selective_scan_fwd_n: null args / n not in 1..16"); return DM_ERR_ARG; }
     dm_scan_fwd_args norm[16];
     for (int i = 0; i < n; ++i) norm[i] = scan_fwd_normalised(args[i]);
-    return mix_launch_n(norm, n, [&](const dm_scan_fwd_args* a) { return dm_selective_scan_fwd(a, stream); },
-                        [](const dm_scan_fwd_args& x, const dm_scan_fwd_args& y) {
-                            using A = dm_scan_fwd_args;
-                            return mix_congruent(x, y, &A::u, &A::delta, &A::z, &A::out, &A::B, &A::C, &A::A, &A::D, &A::delta_bias,
-                                                 &A::z_row_index, &A::out_row_index, &A::ckpt, &A::last_state);
-                        });
+    return mix_run_n("dm_selective_scan_fwd_n", norm, n, stream, check_scan_fwd, pairs_scan_fwd, run_scan_fwd);
 }

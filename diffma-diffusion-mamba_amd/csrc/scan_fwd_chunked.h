@@ -180,11 +180,16 @@ static inline bool use_chunked_fwd(const dm_scan_fwd_args& a) {
     return !a.last_state && a.dstate == 16 && (waves <= 512 || forced == 1) && a.seqlen > 4 * CHUNKED_NW &&
            a.seqlen <= CHUNKED_NW * CHUNKED_LC;
 }
+// the launch goes to this family -- the one forward scan that takes two argument structs (dispatch_fwd, and the pairing rule of
+// dm_selective_scan_fwd_n through scan_fwd_takes_two)
+static inline bool fwd_goes_chunked(const dm_scan_fwd_args& a) {
+    return use_chunked_fwd(a) && (a.bc_dtype == DM_F32 || a.bc_dtype == a.io_dtype);
+}
 
 template <typename T, typename TBC, bool HAS_Z, bool IDX>
-static void launch_fwd_chunked2(const dm_scan_fwd_args& a, hipStream_t st) {
+static void launch_fwd_chunked2(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st) {
     unsigned gz;
-    const mix_args<dm_scan_fwd_args> m = mix_make(a, gz);
+    const mix_args<dm_scan_fwd_args> m = mix_make(a, second, gz);
     dim3 grid((a.dim + WAVE - 1) / WAVE, a.nseq, gz), block(WAVE * CHUNKED_NW);
     const bool sp = (a.flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
     if constexpr (HAS_Z && IDX) {                   // the model's call pattern: also built with checkpoints (small-batch training)
@@ -209,14 +214,14 @@ static void launch_fwd_chunked2(const dm_scan_fwd_args& a, hipStream_t st) {
 }
 
 template <typename T, typename TBC>
-static int launch_fwd_chunked(const dm_scan_fwd_args& a, hipStream_t st) {
+static int launch_fwd_chunked(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st) {
     const bool idx = a.z_row_index != nullptr;
     if (a.z) {
-        if (idx) launch_fwd_chunked2<T, TBC, true, true>(a, st);
-        else launch_fwd_chunked2<T, TBC, true, false>(a, st);
+        if (idx) launch_fwd_chunked2<T, TBC, true, true>(a, second, st);
+        else launch_fwd_chunked2<T, TBC, true, false>(a, second, st);
     } else {
-        if (idx) launch_fwd_chunked2<T, TBC, false, true>(a, st);
-        else launch_fwd_chunked2<T, TBC, false, false>(a, st);
+        if (idx) launch_fwd_chunked2<T, TBC, false, true>(a, second, st);
+        else launch_fwd_chunked2<T, TBC, false, false>(a, second, st);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("dm_selective_scan_fwd (chunked): launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
@@ -224,11 +229,9 @@ static int launch_fwd_chunked(const dm_scan_fwd_args& a, hipStream_t st) {
 }
 
 template <typename T>
-static int dispatch_fwd(const dm_scan_fwd_args& a, hipStream_t st) {
-    if (use_chunked_fwd(a)) {
-        if (a.bc_dtype == DM_F32) return launch_fwd_chunked<T, float>(a, st);
-        if (a.bc_dtype == a.io_dtype) return launch_fwd_chunked<T, T>(a, st);
-    }
+static int dispatch_fwd(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st) {
+    if (fwd_goes_chunked(a)) return a.bc_dtype == DM_F32 ? launch_fwd_chunked<T, float>(a, second, st) : launch_fwd_chunked<T, T>(a, second, st);
+    if (second) { set_error("dm_selective_scan_fwd: the sequential kernel takes one argument struct"); return DM_ERR_ARG; }
     return dispatch_bc<T>(a, st);
 }
 

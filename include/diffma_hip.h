@@ -748,10 +748,12 @@ int dm_gemm_large_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, in
  * A DiffMa block runs TWO mixers on tensors of the same shape with different weights (reference block/mamba_block.py:107-108),
  * and the reference's own configuration trains at one sample per GPU (config/brain.yaml:11), where a step is bound by the
  * NUMBER of kernel launches.  Each function below takes an ARRAY of `n` argument structs and is equivalent to calling its
- * single-launch namesake on args[0], args[1], ... in order.  Neighbouring structs that are congruent -- every size, stride,
- * dtype and flag equal, the same pointers NULL -- share ONE launch when the kernel their shape selects is built for it (all of
- * them except the large-launch sequential scans; the kernel picks its struct by blockIdx.z); anything else is launched one
- * after the other.  The results are bit-identical to the separate calls.  The launches must be independent of each other.
+ * single-launch namesake on args[0], args[1], ... in order, stopping at the first non-zero status.  EVERY struct goes through the
+ * argument checks of the single-launch function before anything is launched for it, whether or not it shares a launch.
+ * Neighbouring structs that are congruent -- every size, stride, dtype and flag equal, the same pointers NULL -- share ONE
+ * launch when the kernel their shape selects is built for it (all of them except the large-launch sequential scans; the kernel
+ * picks its struct by blockIdx.z); anything else is launched one after the other.  The results are bit-identical to the
+ * separate calls.  The launches must be independent of each other.
  * ---------------------------------------------------------------------------------------------- */
 int dm_selective_scan_fwd_n(const dm_scan_fwd_args *args, int n, void *stream);
 int dm_selective_scan_bwd_n(const dm_scan_bwd_args *args, int n, void *stream);

@@ -1414,6 +1414,94 @@ def test_n_entry_points_run_incongruent_launches_one_by_one(gpu):
     torch.testing.assert_close(b, x1.view(-1, 256).sum(0), rtol=1e-5, atol=1e-4)
 
 
+def test_dtproj_n_entries_check_every_struct_like_a_single_call(gpu):
+    """dm_dtproj_softplus_fwd_n / dm_dtproj_bwd_n through the raw C ABI with two structs that are congruent in every size and stride,
+    one of them with `xdbl` (forward) / `ddelta` (backward) starting 8 bytes into a 16-byte aligned buffer.  The kernels move 16-byte
+    pieces, so the single entry rejects that struct (DM_ERR_LAYOUT forward, DM_ERR_ARG backward); the `_n` entry is documented as the
+    single entry on args[0], args[1], ... in order, so: aligned struct first -> that status, the first struct's outputs bit for bit
+    those of a single call, the second struct's outputs untouched; misaligned struct first -> that status and nothing written."""
+    import ctypes
+    from diffma_amd import _lib
+
+    lib = _lib.load()
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    raw = lambda name, a: int(getattr(lib, name)(ctypes.byref(a), stream()))
+
+    def raw_n(name, structs):
+        arr = (type(structs[0]) * len(structs))(*structs)
+        return int(getattr(lib, name)(ctypes.cast(arr, ctypes.c_void_p), len(structs), stream()))
+
+    DM_OK, DM_ERR_ARG, DM_ERR_LAYOUT, SENT = 0, -1, -2, 7.0
+    dt, M, Dm, R, N = torch.bfloat16, 64, 512, 16, 16
+    P, nblk = R + 2 * N, 2
+    g = torch.Generator(device=gpu).manual_seed(5)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, device=gpu, generator=g) * sc)
+
+    def shifted(t):
+        """the same values 8 bytes into a 16-byte aligned buffer (4 spare elements on either side)"""
+        buf = torch.zeros(t.numel() + 8, dtype=t.dtype, device=gpu)
+        assert buf.data_ptr() % 16 == 0
+        v = buf[4:4 + t.numel()].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 8
+        return v
+
+    sent = lambda *s, dtype=dt: torch.full(s, SENT, dtype=dtype, device=gpu)
+    untouched = lambda *ts: all(bool((t == SENT).all()) for t in ts)
+
+    # ---- forward: delta = softplus(xdbl[:, :R] @ w^T + bias)
+    def fwd_args(xdbl, w, bias, delta):
+        a = _lib.dm_dtproj_args()
+        a.rows, a.dim, a.rank, a.io_dtype = M, Dm, R, _lib.DM_BF16
+        a.xdbl, a.w, a.bias, a.delta, a.xd_sr = xdbl.data_ptr(), w.data_ptr(), bias.data_ptr(), delta.data_ptr(), xdbl.stride(0)
+        return a
+
+    x = [rnd(M, P).to(dt), shifted(rnd(M, P).to(dt))]
+    w = [rnd(Dm, R, sc=0.3).to(dt) for _ in range(2)]
+    bias = [rnd(Dm, sc=0.5) for _ in range(2)]
+    ref = sent(M, Dm)
+    assert raw("dm_dtproj_softplus_fwd", fwd_args(x[0], w[0], bias[0], ref)) == DM_OK
+    lone = sent(M, Dm)
+    assert raw("dm_dtproj_softplus_fwd", fwd_args(x[1], w[1], bias[1], lone)) == DM_ERR_LAYOUT
+    for order in ((0, 1), (1, 0)):
+        out = [sent(M, Dm), sent(M, Dm)]
+        rc = raw_n("dm_dtproj_softplus_fwd_n", [fwd_args(x[k], w[k], bias[k], out[k]) for k in order])
+        torch.cuda.synchronize()
+        assert rc == DM_ERR_LAYOUT, (order, rc)
+        assert untouched(out[1], lone), order
+        if order == (0, 1):
+            assert torch.equal(out[0], ref)
+        else:
+            assert untouched(out[0])
+
+    # ---- backward: dxdbl[:, :R] = ddelta @ w, part[blk] = the workgroup's share of ddelta^T @ xdbl[:, :R]
+    def bwd_args(ddelta, xdbl, w, dxdbl, part):
+        a = _lib.dm_dtproj_bwd_args()
+        a.rows, a.dim, a.rank, a.io_dtype, a.nblk = M, Dm, R, _lib.DM_BF16, nblk
+        a.ddelta, a.xdbl, a.w, a.dxdbl, a.part = ddelta.data_ptr(), xdbl.data_ptr(), w.data_ptr(), dxdbl.data_ptr(), part.data_ptr()
+        a.xd_sr, a.dxd_sr = xdbl.stride(0), dxdbl.stride(0)
+        return a
+
+    assert lib.dm_dtproj_bwd_supported(Dm, R, _lib.DM_BF16)
+    dd = [rnd(M, Dm, sc=0.5).to(dt), shifted(rnd(M, Dm, sc=0.5).to(dt))]
+    xb = [rnd(M, P).to(dt) for _ in range(2)]
+    ref_dx, ref_part = sent(M, P), sent(nblk, Dm * R, dtype=torch.float32)
+    assert raw("dm_dtproj_bwd", bwd_args(dd[0], xb[0], w[0], ref_dx, ref_part)) == DM_OK
+    lone_dx, lone_part = sent(M, P), sent(nblk, Dm * R, dtype=torch.float32)
+    assert raw("dm_dtproj_bwd", bwd_args(dd[1], xb[1], w[1], lone_dx, lone_part)) == DM_ERR_ARG
+    for order in ((0, 1), (1, 0)):
+        dx = [sent(M, P), sent(M, P)]
+        part = [sent(nblk, Dm * R, dtype=torch.float32) for _ in range(2)]
+        rc = raw_n("dm_dtproj_bwd_n", [bwd_args(dd[k], xb[k], w[k], dx[k], part[k]) for k in order])
+        torch.cuda.synchronize()
+        assert rc == DM_ERR_ARG, (order, rc)
+        assert untouched(dx[1], part[1], lone_dx, lone_part), order
+        if order == (0, 1):
+            assert torch.equal(dx[0], ref_dx) and torch.equal(part[0], ref_part)
+        else:
+            assert untouched(dx[0], part[0])
+
+
 # ---- dm_gemm: the projections' dense products in the small-launch regime (csrc/gemm.hip) -------------------------------------
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M", [196, 1568, 200, 4704])
