@@ -7,7 +7,7 @@
 //     both -- the kernel takes an ARRAY of argument structs and picks its own by blockIdx.z (dm_gemm_n, dm_common.h mix_args);
 //   * the vendor library cannot be trusted with the batch-2 form: torch.bmm of [2, 12544, 1024] x [2, 1024, 512] returns NaN with
 //     the library's default kernel, and TunableOp's tuning loop faults on three more of these shapes (MI355X, ROCm 7.2; probe:
-//     tools/dbg_bmm.py);
+//     DESIGN.md section 7);
 //   * its single GEMMs take 12-20 us each at M = 1568 (tile quantisation: a 256 x 256 tile grid does not fill 256 CUs).
 // Large batches stay on the library (solution table, split-K): this kernel is a 2-barrier LDS-staged structure, not a
 // 256 x 256 8-phase pipeline.

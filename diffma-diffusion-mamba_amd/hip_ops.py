@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -81,72 +82,61 @@ def set_timer(timer):
     return prev
 
 
-class paired:
-    """Context manager that makes the two mixers of a DiffMa block share their kernel launches (reference block/mamba_block.py:107-108
-    runs them one after the other; at the reference's own batch -- config/brain.yaml, one sample per GPU -- a step is bound by the
-    number of launches).  Inside the block the C-ABI launches of this module are QUEUED instead of issued; the caller runs the same
-    wrapper calls first for mixer 0, then for mixer 1; at exit launch i of mixer 0 and launch i of mixer 1 go out as ONE call of the
-    kernel's `_n` entry point (include/diffma_hip.h, ABI 25), which puts congruent launches into one grid (blockIdx.z picks the
-    argument struct) and falls back to two launches otherwise.  Results are bit-identical to the unpaired calls.
-    Rules for the code inside: only wrapper calls, allocations and views -- no torch arithmetic on their outputs (they have not
-    been computed yet); a wrapper that has to fall back to torch arithmetic calls `_pair_flush()` first, which issues everything
-    queued so far one by one and turns the rest of the block into immediate launches.  Every tensor whose pointer went into a
-    queued argument struct is kept alive until the launch (`_ptr`)."""
-
-    def __init__(self, enabled=True):
-        self.enabled = enabled
-        self.queue, self.keep, self.broken, self.mark = [], [], False, None
-
-    def __enter__(self):
-        if self.enabled:
-            if _pair() is not None:
-                raise RuntimeError("hip_ops.paired() does not nest")
-            _TLS.pair = self
-        return self
-
-    def second(self):
-        """Call between the first and the second mixer's wrapper calls."""
-        self.mark = len(self.queue)
-
-    def __exit__(self, et, ev, tb):
-        if not self.enabled:
-            return False
-        _TLS.pair = None
-        if et is None:
-            self.flush(pairwise=True)
-        self.queue, self.keep = [], []
-        return False
-
-    def flush(self, pairwise=False):
-        q, self.queue = self.queue, []
-        k = self.mark
-        if pairwise and not self.broken and k is not None and len(q) == 2 * k and all(q[i][0] == q[i + k][0] for i in range(k)):
-            for i in range(k):
-                name, a0, tensor, nbytes, design, flops = q[i]
-                _issue(name, [a0, q[i + k][1]], tensor, nbytes + q[i + k][3], None if design is None else design + (q[i + k][4] or 0),
-                       flops + q[i + k][5])
-        else:
-            for name, a, tensor, nbytes, design, flops in q:
-                _issue(name, [a], tensor, nbytes, design, flops)
-        self.keep = []
-        self.mark = None
+_TLS = threading.local()          # a stage belongs to the thread that opened it: the backward runs on autograd's worker thread
 
 
-import threading
+def _stage():
+    return getattr(_TLS, "stage", None)
 
-_TLS = threading.local()          # the queue belongs to the thread that opened it: the backward runs on autograd's worker thread
+
+class _Stage:
+    """What one both() call has recorded: the launches of fn(0) and of fn(1), and every tensor their argument structs name."""
+
+    def __init__(self):
+        self.queues, self.g, self.keep = ([], []), 0, []          # g: the queue being filled; None = launch immediately
+
+    def singly(self):
+        q, self.queues = self.queues[0] + self.queues[1], ([], [])
+        for name, a, tensor, nbytes, design, flops in q:
+            _issue(name, [a], tensor, nbytes, design, flops)
 
 
-def _pair():
-    return getattr(_TLS, "pair", None)
+def both(fn, enabled=True):
+    """(fn(0), fn(1)); launch i of fn(0) and launch i of fn(1) leave as ONE dm_*_n call when they name the same entry point.
+    The two mixers of a DiffMa block share their kernel launches this way (reference block/mamba_block.py:107-108 runs them one after
+    the other; at its own batch -- config/brain.yaml, one sample per GPU -- a step is bound by the number of launches).  The C-ABI
+    launches fn makes are QUEUED and go out after fn(1): the `_n` entry point (include/diffma_hip.h, ABI 25) puts congruent launches
+    into one grid (blockIdx.z picks the argument struct).  If the two calls did not queue the same entry points in the same order,
+    fn(0)'s launches go out one by one, then fn(1)'s.  Results are bit-identical to the unpaired calls.  Does not nest.
+    Rules for fn: only wrapper calls, allocations and views -- no torch arithmetic on their outputs (not computed yet); a wrapper
+    that has to fall back to torch arithmetic calls `_pair_flush()` first.  `_ptr` keeps every tensor named in a queued struct alive."""
+    if not enabled:
+        return fn(0), fn(1)
+    if _stage() is not None:
+        raise RuntimeError("hip_ops.both() does not nest")
+    st = _TLS.stage = _Stage()
+    try:
+        r0 = fn(0)
+        if st.g is not None:
+            st.g = 1
+        r1 = fn(1)
+    finally:
+        _TLS.stage = None
+    q0, q1 = st.queues
+    if len(q0) == len(q1) and all(l0[0] == l1[0] for l0, l1 in zip(q0, q1)):
+        for (name, a0, tensor, nbytes, design, flops), l1 in zip(q0, q1):
+            _issue(name, [a0, l1[1]], tensor, nbytes + l1[3], None if design is None else design + (l1[4] or 0), flops + l1[5])
+    else:
+        st.singly()
+    return r0, r1
 
 
 def _pair_flush():
     """A wrapper is about to do torch arithmetic on launch outputs: issue what is queued (unpaired) and stop queueing."""
-    pr = _pair()
-    if pr is not None:
-        pr.flush()
-        pr.broken = True
+    st = _stage()
+    if st is not None and st.g is not None:
+        st.g = None
+        st.singly()
 
 
 _DEBUG_SYNC = os.environ.get("DIFFMA_DEBUG_SYNC", "0") == "1"      # developer aid: synchronise and name every C-ABI launch
@@ -176,9 +166,9 @@ def _launch(name, args, tensor, nbytes, design_bytes=None, flops=0):
     """nbytes: ALGORITHMIC bytes of the launch (SURVEY.md 8d: what any implementation of the operator must move);
     design_bytes: the bytes THIS implementation moves by design (algorithmic + checkpoints + partial rows), if different;
     flops: for the matrix-pipe kernels whose roof is the MFMA peak (dm_gemm)."""
-    pr = _pair()
-    if pr is not None and not pr.broken:
-        pr.queue.append((name, args, tensor, nbytes, design_bytes, flops))
+    st = _stage()
+    if st is not None and st.g is not None:
+        st.queues[st.g].append((name, args, tensor, nbytes, design_bytes, flops))
         return
     _issue(name, [args], tensor, nbytes, design_bytes, flops)
 
@@ -205,9 +195,9 @@ def _stream(t: torch.Tensor) -> int:
 def _ptr(t):
     if t is None:
         return 0
-    pr = _pair()
-    if pr is not None:
-        pr.keep.append(t)              # the launch is deferred: the tensor must outlive the wrapper call that named it
+    st = _stage()
+    if st is not None:
+        st.keep.append(t)              # the launch is deferred: the tensor must outlive the wrapper call that named it
     return t.data_ptr()
 
 
@@ -427,13 +417,13 @@ def sum_partials(parts, out):
     return out
 
 
-_COLSUM_SMALL = os.environ.get("DIFFMA_COLSUM_SMALL", "1") == "1"
+COLSUM_SPLIT = os.environ.get("DIFFMA_COLSUM_SPLIT", "1") == "1"        # 0: one workgroup per 256 columns whatever the shape (A/B runs)
 
 
-def colsum(x, small=False):
+def colsum(x):
     """x [R, C] fp32 contiguous -> [C] = x.sum(0) (dm_colsum_f32: ATen's outer-dimension reduction is 4x off HBM speed here)."""
     R, C = x.shape
-    if C % 4 != 0 or not x.is_contiguous() or x.dtype != torch.float32 or (small and not _COLSUM_SMALL):
+    if C % 4 != 0 or not x.is_contiguous() or x.dtype != torch.float32:
         _pair_flush()
         return x.sum(0)
     # The kernel gives every 256 columns ONE workgroup: a tall, narrow matrix (the conv backward's db partial rows at the Mamba-2 width:
@@ -448,9 +438,6 @@ def colsum(x, small=False):
         if rb > 1:
             return _colsum_launch(_colsum_launch(x.view(R // rb, rb * C)).view(rb, C))
     return _colsum_launch(x)
-
-
-COLSUM_SPLIT = os.environ.get("DIFFMA_COLSUM_SPLIT", "1") == "1"        # 0: one workgroup per 256 columns whatever the shape (A/B runs)
 
 
 def _colsum_launch(x):
@@ -654,7 +641,7 @@ def gather_conv1d_bwd(x, weight, bias, dout, *, row_index=None, ndir=1, silu=Tru
     a.part_ss = Dm * (W + 1)
     _launch("dm_gather_conv1d_bwd", a, x, 3 * ndir * Bsz * L * Dm * x.element_size())
     # partial rows -> ONE column sum (ATen's reduction of these shapes takes ~21 us per call, dm_colsum_f32 ~5)
-    psum = colsum(part, True)
+    psum = colsum(part)
     return dx, psum[:Dm * W].view(Dm, W), psum[Dm * W:]
 
 
@@ -970,7 +957,7 @@ def ln_mod_bwd(x, x2, gamma, beta, shift, scale, mask, eps, stats, dy1, dy2, dx=
     has_old = dx_add is not None or bool(accumulate)
     _launch("dm_ln_mod_bwd", a, x, Bsz * L * C * ((3 if has_old else 2) * x.element_size() + dy1.element_size() * (2 if dy2 is not None else 1)))
     if scale is None and shift is None:       # no modulation (the LayerNorm of the fusion MLP): only d gamma / d beta are wanted -- one
-        pg = colsum(part.view(Bsz * bpb, 4 * C), True).view(4, C)      # column sum over all partial rows instead of two reductions
+        pg = colsum(part.view(Bsz * bpb, 4 * C)).view(4, C)      # column sum over all partial rows instead of two reductions
         return dx, dx2, None, None, pg[2], pg[3]
     if mod_dtype is not None and mod_dtype != torch.float32:
         ds = part[:, :, :2].sum(1, dtype=mod_dtype)                    # [B, 2, C] in the consumer's dtype: one launch
@@ -1111,7 +1098,7 @@ def rmsnorm_merge_bwd(y, weight, eps, rstd, dout):
     a.rstd, a.dout, a.dy, a.dw_part = _ptr(rstd), _ptr(dout), _ptr(dy), _ptr(part)
     a.dout_sr, a.dy_ss, a.dy_sr = C, dy.stride(0), C
     _launch("dm_rmsnorm_merge_bwd", a, y, (2 * K + 1) * Bsz * L * C * y.element_size())
-    return dy, colsum(part, True)
+    return dy, colsum(part)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1298,4 +1285,4 @@ def ssd_bwd(x, Bm, Cm, dt_tok, z, dout, A_h, D_h, dt_bias_h, *, z_row_index=None
     es = x.element_size()
     _launch("dm_ssd_bwd", a, x, (6 if z is not None else 3) * S * L * Din * es + 2 * S * L * 16 * es + S * H * L * 32 * 4)
     dbc_sum = colsum(dbc.view(H, S * L * 32)).view(S, L, 32) if H > 1 else dbc.view(S, L, 32)
-    return dx, dz, dbc_sum, ddt, colsum(dad.view(S, 3 * H), True).view(3, H)
+    return dx, dz, dbc_sum, ddt, colsum(dad.view(S, 3 * H)).view(3, H)

@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import hip_ops
+from . import _lib, hip_ops
 from .step_prep import cast_weight, stacked_pair
 
 
@@ -215,7 +215,7 @@ def _mm_f32(x, y):
     """x @ y in fp32 from 16-bit operands WITHOUT a separate cast launch where the library offers it (hipBLASLt accumulates in fp32
     anyway; the 16-bit result + `.float()` of the plain form rounds the weight gradient once more and costs a launch per GEMM -- ~150 per
     training step, which is what a small-batch step is made of)."""
-    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and _MM_F32[0] is not False and os.environ.get("DIFFMA_MM_F32", "1") == "1":
+    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and _MM_F32[0] is not False:
         try:
             out = torch.mm(x, y, out_dtype=torch.float32)
             _MM_F32[0] = True
@@ -251,7 +251,7 @@ def _own_single(a, b, a_kmajor, b_kmajor, out_dtype=None):
     """dm_gemm for ONE product: same row bound as the paired form, and only for matrices with at least 64 rows (below that a GEMM
     is a handful of workgroups either way)."""
     rows = a.shape[0]
-    return (PAIR_GEMM == "own" and 64 <= rows <= PAIR_OWN_MAX_ROWS and a.dim() == 2 and b.dim() == 2
+    return (64 <= rows <= PAIR_OWN_MAX_ROWS and a.dim() == 2 and b.dim() == 2
             and hip_ops.gemm_supported(a, b, a_kmajor, b_kmajor, out_dtype))
 
 
@@ -475,66 +475,31 @@ class _SpiralSSMFn(torch.autograd.Function):
 # The reference runs mamba1(x_ssm) and mamba2(w_ssm) one after the other: same shapes, different weights and spiral tables.  Its own
 # configuration trains at ONE sample per GPU (config/brain.yaml:11), where a step is bound by the number of kernel launches (eager:
 # the host's launch rate; hipGraph: ~8 us of dispatch per node), not by what the kernels do.  The pair path issues every stage once
-# for both mixers: the projections as batched GEMMs over stacked weights, the kernels through hip_ops.paired() -> the `_n` entry
+# for both mixers: the projections as batched GEMMs over stacked weights, the kernels through hip_ops.both() -> the `_n` entry
 # points of the C ABI (one grid, blockIdx.z picks the mixer).  Arithmetic per mixer is unchanged: kernels bit-identical, GEMMs to
 # library rounding.  Used for small launches only (below the fused conv + x_proj threshold); large batches gain nothing from it.
 PAIR_MIXERS = os.environ.get("DIFFMA_PAIR_MIXERS", "1") == "1"
 
-# How the pair path multiplies by the two mixers' projection weights.
-#   "own" (default): dm_gemm (csrc/gemm.hip), ONE launch for both mixers through hip_ops.paired() -- up to PAIR_OWN_MAX_ROWS rows per
-#          mixer, where it is also faster on the device than the library's two GEMMs (DiffMa-L/2 widths, both mixers, us incl. launch,
-#          tools/bench_gemm_own.py: batch 8 in_proj 43 -> 21 forward, 42 -> 30 weight gradient, out_proj 41 -> 16 / 38 -> 15 / 40 -> 22;
-#          from ~6 000 rows the library's large tiles win); above that, and for shapes dm_gemm does not take, "mm".
-#   "mm":  one plain library GEMM per mixer -- the products the unpaired path has always issued, tuned and recorded.
-#   "bmm": ONE batched library GEMM per product (batch = 2), TunableOp's first-use tuning switched off around the call.  NOT safe:
-#          torch.bmm([2, 12544, 1024] x [2, 1024, 512]) -- out_proj at batch 64 -- returns NaN / faults with the library's DEFAULT kernel
-#          (MI355X, ROCm 7.2, tools/dbg_bmm.py, each case in its own process), while M = 196, 1568, 3136 and 33320 of the same product
-#          are correct; under the tuning loop [2, 4704, 1024] x [2, 1024, 64] and the one-sample in_proj / out_proj shapes fault too.
-PAIR_GEMM = os.environ.get("DIFFMA_PAIR_GEMM", "own")
+# The pair path's projections run on dm_gemm (csrc/gemm.hip), ONE launch for both mixers through hip_ops.both(), up to PAIR_OWN_MAX_ROWS
+# rows per mixer, where it is also faster on the device than the library's two GEMMs (DiffMa-L/2 widths, both mixers, us incl. launch,
+# tools/bench_gemm_own.py: batch 8 in_proj 43 -> 21 forward, 42 -> 30 weight gradient, out_proj 41 -> 16 / 38 -> 15 / 40 -> 22; from
+# ~6 000 rows the library's large tiles win).  Above that, and for shapes dm_gemm does not take: one plain library GEMM per mixer --
+# the products the unpaired path has always issued, tuned and recorded (a batch-2 library GEMM is not safe here: DESIGN.md section 7).
 PAIR_OWN_MAX_ROWS = int(os.environ.get("DIFFMA_PAIR_OWN_MAX_ROWS", "3200"))
 
 
-def _pair_use_bmm(t):
-    return PAIR_GEMM == "bmm"
-
-
 def _pair_use_own(rows, a, b, a_kmajor, b_kmajor, out_dtype=None):
-    return PAIR_GEMM == "own" and rows <= PAIR_OWN_MAX_ROWS and hip_ops.gemm_supported(a, b, a_kmajor, b_kmajor, out_dtype)
+    return rows <= PAIR_OWN_MAX_ROWS and hip_ops.gemm_supported(a, b, a_kmajor, b_kmajor, out_dtype)
 
 
 def _own_pair(a, b, a_kmajor, b_kmajor, out, accumulate=False):
     """out[g] (+)= opA(a[g]) @ opB(b[g]) for g = 0, 1 in ONE launch (dm_gemm_n)."""
-    with hip_ops.paired() as pr:
-        for g in (0, 1):
-            if g:
-                pr.second()
-            hip_ops.gemm(a[g], b[g], a_kmajor, b_kmajor, out=out[g], accumulate=accumulate)
+    hip_ops.both(lambda g: hip_ops.gemm(a[g], b[g], a_kmajor, b_kmajor, out=out[g], accumulate=accumulate))
     return out
 
 
-def _bmm_untuned(x, y, out_dtype=None):
-    tun = torch.cuda.tunable if x.is_cuda else None
-    was = tun is not None and tun.is_enabled() and tun.tuning_is_enabled()
-    if was:
-        tun.tuning_enable(False)
-    try:
-        if out_dtype is None or out_dtype == x.dtype:
-            return torch.bmm(x, y)
-        try:
-            return torch.bmm(x, y, out_dtype=out_dtype)
-        except (RuntimeError, NotImplementedError, TypeError):
-            return torch.bmm(x, y).to(out_dtype)
-    finally:
-        if was:
-            tun.tuning_enable(True)
-
-
-def _pair_matmul(x, y, out_dtype=None):
-    """x [2, P, Q] @ y [2, Q, R] -> [2, P, R]: one batched GEMM, or one GEMM per mixer (see PAIR_GEMM)."""
-    if _pair_use_bmm(x):
-        return GemmChain.run(_bmm_untuned, x, y, out_dtype)
-    if out_dtype == torch.float32 and x.dtype != torch.float32:
-        return (_mm_f32(x[0], y[0]), _mm_f32(x[1], y[1]))      # indexable like a [2, ...] tensor: the caller only takes [0] and [1]
+def _pair_matmul(x, y):
+    """x [2, P, Q] @ y [2, Q, R] -> [2, P, R]: one library GEMM per mixer."""
     out = torch.empty((2, x.shape[1], y.shape[2]), dtype=x.dtype, device=x.device)
     for g in (0, 1):
         GemmChain.run(torch.mm, x[g], y[g], out=out[g])
@@ -587,8 +552,6 @@ class _LinearPairFn(torch.autograd.Function):
                 dx = dx.to(x_dt)
             if _pair_use_own(M, dy[0], x2[0], False, False, torch.float32):
                 dW = _own_pair(dy, x2, False, False, torch.empty((2, N, K), dtype=torch.float32, device=dy.device))
-            elif _pair_use_bmm(dy):
-                dW = _pair_matmul(dy.transpose(1, 2), x2, torch.float32)                                   # [2, N, K] fp32
             else:
                 dW = (_tn_splitk(dy[0], x2[0]), _tn_splitk(dy[1], x2[1]))                                  # the unpaired path's products
             dW0, dW1 = (dW[0], dW[1]) if w_dt == torch.float32 else (dW[0].to(w_dt), dW[1].to(w_dt))
@@ -617,13 +580,9 @@ class _SpiralSSMPairFn(torch.autograd.Function):
         cw, cb, bias, A, Dk = (cw0, cw1), (cb0, cb1), (b0, b1), (A0, A1), (D0, D1)
         Wx_st, Wdt_st = stacked_pair(Wx0, Wx1, dt_), stacked_pair(Wdt0, Wdt1, dt_)       # [2, R+2N, Din], [2, Din, R]
         xc = torch.empty((2, S, L, Din), dtype=dt_, device=dev)
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                hip_ops.gather_conv1d_fwd(xz[g][..., :Din], cw[g], cb[g], row_index=idx[g], ndir=ndir, silu=True, out=xc[g])
+        hip_ops.both(lambda g: hip_ops.gather_conv1d_fwd(xz[g][..., :Din], cw[g], cb[g], row_index=idx[g], ndir=ndir, silu=True, out=xc[g]))
         # x_proj stays one product per mixer: as a batch-2 GEMM its [M, 1024] x [1024, 64] shape makes TunableOp's first-use tuning
-        # run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop, tools/dbg_bmm.py);
+        # run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop);
         # the plain products below are the ones the unpaired path has always issued
         x_dbl = torch.empty((2, M, R + 2 * N), dtype=dt_, device=dev)
         xc2 = xc.view(2, M, Din)
@@ -632,28 +591,16 @@ class _SpiralSSMPairFn(torch.autograd.Function):
         else:
             for g in (0, 1):
                 GemmChain.run(torch.mm, xc2[g], Wx_st[g].t(), out=x_dbl[g])
-        delta = [None, None]
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                delta[g] = hip_ops.dtproj_softplus_fwd(x_dbl[g], Wdt_st[g], bias[g]).view(S, L, Din)
+        delta = hip_ops.both(lambda g: hip_ops.dtproj_softplus_fwd(x_dbl[g], Wdt_st[g], bias[g]).view(S, L, Din))
         ckpt = [hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev) if need_grad else None for _ in (0, 1)]
         xd3 = x_dbl.view(2, S, L, R + 2 * N)
-        ydir = [None, None]
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                ydir[g] = hip_ops.scan_fwd(xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], True,
-                                           z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, ckpt=ckpt[g], delta_activated=True)
+        ydir = hip_ops.both(lambda g: hip_ops.scan_fwd(
+            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], True,
+            z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, ckpt=ckpt[g], delta_activated=True))
         y = torch.empty((2, Bsz, L, Din), dtype=dt_, device=dev)
         pre = torch.empty((2, Bsz, L, Din), dtype=dt_, device=dev) if need_grad else None
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                hip_ops.token_merge(ydir[g].view(ndir, Bsz, L, Din), gate=xz[g][..., Din:], pre_out=None if pre is None else pre[g], out=y[g])
+        hip_ops.both(lambda g: hip_ops.token_merge(ydir[g].view(ndir, Bsz, L, Din), gate=xz[g][..., Din:],
+                                                   pre_out=None if pre is None else pre[g], out=y[g]))
         if need_grad:
             ctx.save_for_backward(xz0, xz1, idx0, idx1, cw0, cw1, cb0, cb1, b0, b1, A0, A1, D0, D1, Wx_st, Wdt_st, xc, x_dbl,
                                   delta[0], delta[1], ckpt[0], ckpt[1], pre)
@@ -676,33 +623,20 @@ class _SpiralSSMPairFn(torch.autograd.Function):
         dxz = torch.empty((2, Bsz, L, D2), dtype=dt_, device=dev)
         dx_dbl = torch.empty((2, M, R + 2 * N), dtype=dt_, device=dev)
         xd3 = x_dbl.view(2, S, L, R + 2 * N)
-        gate_g = [None, None]
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                gate_g[g], _ = hip_ops.gate_bwd(dy[g], xz[g][..., Din:], pre[g], dz_out=dxz[g][..., Din:])
+        gate_g = hip_ops.both(lambda g: hip_ops.gate_bwd(dy[g], xz[g][..., Din:], pre[g], dz_out=dxz[g][..., Din:])[0])
         du = torch.empty((2, S, L, Din), dtype=dt_, device=dev)
-        res = [None, None]
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                res[g] = hip_ops.scan_bwd(xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], gate_g[g], ckpt[g],
-                                          True, z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, du_out=du[g],
-                                          dbc_out=dx_dbl[g].view(S, L, R + 2 * N)[..., R:], delta_activated=True)
+        res = hip_ops.both(lambda g: hip_ops.scan_bwd(
+            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], gate_g[g], ckpt[g], True,
+            z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, du_out=du[g],
+            dbc_out=dx_dbl[g].view(S, L, R + 2 * N)[..., R:], delta_activated=True))
         ddelta = [res[g][1].view(M, Din) for g in (0, 1)]
-        dWdt = [None, None]
         if hip_ops.dtproj_bwd_supported(ddelta[0], x_dbl[0], Wdt_st[0], dx_dbl[0]):
-            with hip_ops.paired() as pr:
-                for g in (0, 1):
-                    if g:
-                        pr.second()
-                    dWdt[g] = hip_ops.dtproj_bwd(ddelta[g], x_dbl[g], Wdt_st[g], dx_dbl[g])
+            dWdt = hip_ops.both(lambda g: hip_ops.dtproj_bwd(ddelta[g], x_dbl[g], Wdt_st[g], dx_dbl[g]))
         else:
+            dWdt = []
             for g in (0, 1):
                 dx_dbl[g][:, :R] = GemmChain.run(torch.mm, ddelta[g], Wdt_st[g])
-                dWdt[g] = _tn_splitk(ddelta[g], x_dbl[g][:, :R])
+                dWdt.append(_tn_splitk(ddelta[g], x_dbl[g][:, :R]))
         xc2 = xc.view(2, M, Din)
         if _pair_use_own(M // 4, dx_dbl[0], xc2[0], False, False, torch.float32):
             dWx = _own_pair(dx_dbl, xc2, False, False, torch.empty((2, R + 2 * N, Din), dtype=torch.float32, device=dev))
@@ -715,17 +649,8 @@ class _SpiralSSMPairFn(torch.autograd.Function):
             for g in (0, 1):
                 GemmChain.run(du2[g].addmm_, dx_dbl[g], Wx_st[g])
         dxc = du
-        cres = [None, None]
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                cres[g] = hip_ops.gather_conv1d_bwd(xz[g][..., :Din], cw[g], cb[g], dxc[g], row_index=idx[g], ndir=ndir, silu=True)
-        with hip_ops.paired() as pr:
-            for g in (0, 1):
-                if g:
-                    pr.second()
-                hip_ops.token_merge(cres[g][0].view(ndir, Bsz, L, Din), out=dxz[g][..., :Din])
+        cres = hip_ops.both(lambda g: hip_ops.gather_conv1d_bwd(xz[g][..., :Din], cw[g], cb[g], dxc[g], row_index=idx[g], ndir=ndir, silu=True))
+        hip_ops.both(lambda g: hip_ops.token_merge(cres[g][0].view(ndir, Bsz, L, Din), out=dxz[g][..., :Din]))
         out = [dxz[0], dxz[1], None, None, None]
         per = lambda f: [f(0), f(1)]
         out += per(lambda g: cres[g][1].to(cw[g].dtype).reshape(cw[g].shape))
@@ -753,7 +678,6 @@ def spiral_ssm_pair_supported(Bsz, L, dtype, mix0, mix1):
     if idx0.shape[0] * Bsz >= hip_ops.XPROJ_FUSED_MIN_SEQS:
         return False
     Din, R = mix0.dt_proj.weight.shape
-    from . import _lib
     code = {torch.bfloat16: _lib.DM_BF16, torch.float16: _lib.DM_F16}[dtype]
     return bool(hip_ops.DTPROJ_FUSED and (R + 2 * 16) % 8 == 0 and _lib.load().dm_dtproj_softplus_supported(int(Din), int(R), code))
 

@@ -659,3 +659,172 @@ def test_bench_plain_run_options_and_output_sample():
     assert s.dtype == torch.float32 and 0 < s.numel() <= 10000
     assert torch.equal(s, bench.fixed_sample([p.clone() for p in ps], 10000, 0))
     assert torch.equal(bench.fixed_sample(ps, 10 ** 6, 0), torch.cat([p.reshape(-1).float() for p in ps]))     # small enough: all of it
+
+
+# ---- hip_ops.both: the queue that lets the two mixers of a block share their launches (no GPU, no library: _issue is recorded) ----
+@pytest.fixture
+def issued(monkeypatch):
+    """Every hip_ops._issue call as (name, structs, nbytes, design_bytes, flops), in order."""
+    from diffma_amd import hip_ops
+
+    log = []
+    monkeypatch.setattr(hip_ops, "_issue", lambda name, arg_list, tensor, nbytes, design_bytes, flops=0:
+                        log.append((name, list(arg_list), nbytes, design_bytes, flops)))
+    return log
+
+
+_ANCHOR = torch.zeros(1)         # the tensor whose device / stream a launch would take
+
+
+def _queue(name, struct, nbytes=1, design=None, flops=0):
+    from diffma_amd import hip_ops
+
+    hip_ops._launch(name, struct, _ANCHOR, nbytes, design, flops)
+
+
+def test_both_issues_congruent_stages_pair_by_pair_with_summed_accounting(issued):
+    from diffma_amd import hip_ops
+
+    def fn(g):
+        _queue("dm_a", f"a{g}", 10 + g, 100 + g, 1000 + g)
+        _queue("dm_b", f"b{g}", 20 + g)
+        _queue("dm_a", f"c{g}", 30 + g, 300 + g)
+        assert issued == []                                  # nothing leaves before both calls have returned
+        return f"r{g}"
+
+    assert hip_ops.both(fn) == ("r0", "r1")
+    assert issued == [("dm_a", ["a0", "a1"], 21, 201, 2001), ("dm_b", ["b0", "b1"], 41, None, 0), ("dm_a", ["c0", "c1"], 61, 601, 0)]
+
+
+def test_both_falls_back_to_single_launches_mixer_0_first(issued):
+    from diffma_amd import hip_ops
+
+    def lengths(g):                                          # mixer 1 queues one launch more
+        for i in range(2 + g):
+            _queue("dm_a", f"a{g}{i}", 10 * g + i, 7, 3)
+
+    hip_ops.both(lengths)
+    assert issued == [("dm_a", [s], n, 7, 3) for s, n in (("a00", 0), ("a01", 1), ("a10", 10), ("a11", 11), ("a12", 12))]
+    del issued[:]
+
+    def names(g):                                            # same length, another entry point at position 1
+        _queue("dm_a", f"a{g}")
+        _queue("dm_b" if g else "dm_c", f"b{g}")
+        _queue("dm_a", f"c{g}")
+
+    hip_ops.both(names)
+    assert [(n, s) for n, s, *_ in issued] == [("dm_a", ["a0"]), ("dm_c", ["b0"]), ("dm_a", ["c0"]),
+                                               ("dm_a", ["a1"]), ("dm_b", ["b1"]), ("dm_a", ["c1"])]
+
+
+def test_pair_flush_issues_the_queue_singly_and_the_rest_immediately(issued):
+    from diffma_amd import hip_ops
+
+    def fn(g):
+        if g == 0:
+            _queue("dm_a", "a0", 5, 6, 7)
+            _queue("dm_b", "b0")
+            assert issued == []
+            hip_ops._pair_flush()
+            assert issued == [("dm_a", ["a0"], 5, 6, 7), ("dm_b", ["b0"], 1, None, 0)]      # out before _pair_flush returns
+        _queue("dm_c", f"c{g}")
+        assert issued[-1] == ("dm_c", [f"c{g}"], 1, None, 0)                                 # immediate, fn(1) included
+        hip_ops._pair_flush()                                                                # a second flush has nothing to do
+        _queue("dm_d", f"d{g}")
+        assert issued[-1][:2] == ("dm_d", [f"d{g}"])
+
+    hip_ops.both(fn)
+    assert [s for _, s, *_ in issued] == [["a0"], ["b0"], ["c0"], ["d0"], ["c1"], ["d1"]]
+    del issued[:]
+
+    def late(g):                                             # flushed inside fn(1): mixer 0's queue first, then mixer 1's
+        _queue("dm_a", f"a{g}")
+        if g:
+            hip_ops._pair_flush()
+            assert [s for _, s, *_ in issued] == [["a0"], ["a1"]]
+
+    hip_ops.both(late)
+    assert [s for _, s, *_ in issued] == [["a0"], ["a1"]]
+
+
+def test_both_issues_nothing_after_an_exception_and_works_again(issued):
+    from diffma_amd import hip_ops
+
+    def fn(g):
+        _queue("dm_a", f"a{g}")
+        if g:
+            raise ValueError("mixer 1")
+
+    with pytest.raises(ValueError, match="mixer 1"):
+        hip_ops.both(fn)
+    assert issued == []
+    _queue("dm_x", "x")                                      # no recorder left behind: a plain launch leaves at once
+    assert issued == [("dm_x", ["x"], 1, None, 0)]
+    hip_ops.both(lambda g: _queue("dm_a", f"n{g}", 2, 3, 4))
+    assert issued[1:] == [("dm_a", ["n0", "n1"], 4, 6, 8)]
+
+
+def test_both_does_not_nest(issued):
+    from diffma_amd import hip_ops
+
+    with pytest.raises(RuntimeError, match="nest"):
+        hip_ops.both(lambda g: hip_ops.both(lambda k: _queue("dm_a", f"a{g}{k}")))
+    assert issued == []
+    hip_ops.both(lambda g: _queue("dm_a", f"a{g}"))
+    assert issued == [("dm_a", ["a0", "a1"], 2, None, 0)]
+
+
+def test_both_in_a_second_thread_has_its_own_queue(issued):
+    """The backward runs on autograd's thread: a stage there must neither see nor disturb one that is open on the main thread."""
+    import threading
+
+    from diffma_amd import hip_ops
+
+    errors = []
+
+    def other():
+        try:
+            hip_ops.both(lambda g: _queue("dm_t", f"t{g}"))
+        except Exception as e:                               # (a shared recorder would raise "does not nest")
+            errors.append(e)
+
+    def fn(g):
+        _queue("dm_a", f"a{g}")
+        if g == 0:
+            th = threading.Thread(target=other)
+            th.start()
+            th.join()
+            assert errors == [] and issued == [("dm_t", ["t0", "t1"], 2, None, 0)]
+
+    hip_ops.both(fn)
+    assert issued == [("dm_t", ["t0", "t1"], 2, None, 0), ("dm_a", ["a0", "a1"], 2, None, 0)]
+
+
+def test_both_disabled_launches_immediately(issued):
+    from diffma_amd import hip_ops
+
+    def fn(g):
+        _queue("dm_a", f"a{g}", 3, 4, 5)
+        assert issued[-1] == ("dm_a", [f"a{g}"], 3, 4, 5)
+        return g
+
+    assert hip_ops.both(fn, enabled=False) == (0, 1)
+    assert issued == [("dm_a", ["a0"], 3, 4, 5), ("dm_a", ["a1"], 3, 4, 5)]
+
+
+def test_both_keeps_the_tensors_of_queued_structs_alive_until_the_launch(monkeypatch):
+    import weakref
+
+    from diffma_amd import hip_ops
+
+    refs, alive = [], []
+    monkeypatch.setattr(hip_ops, "_issue", lambda name, arg_list, *rest: alive.append([r() is not None for r in refs]))
+
+    def fn(g):
+        tmp = torch.full((4,), float(g))                     # a temporary of the wrapper: only its address goes into the struct
+        refs.append(weakref.ref(tmp))
+        _queue("dm_a", hip_ops._ptr(tmp))
+
+    hip_ops.both(fn)
+    assert alive == [[True, True]]
+    assert [r() for r in refs] == [None, None]               # released with the stage

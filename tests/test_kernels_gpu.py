@@ -1284,7 +1284,7 @@ def test_dtproj_bwd_unsupported_shapes_fall_back(gpu):
 
 # ---- several congruent launches in one (dm_*_n entry points, ABI 25): the two mixers of a block ------------------------------
 def test_paired_launches_are_bit_identical_to_separate_ones(gpu):
-    """hip_ops.paired() queues the launches of two independent, congruent calls and issues each pair as ONE `_n` launch (blockIdx.z
+    """hip_ops.both() queues the launches of two independent, congruent calls and issues each pair as ONE `_n` launch (blockIdx.z
     picks the argument struct).  Every kernel of the small-launch mixer path -- gather + conv forward / backward, dt_proj + softplus
     and its backward, the chunk-parallel scans, gated merge, gate backward, partial-row sums -- must produce exactly the bits of
     two separate launches, and the pair must really share launches (counted at the library call)."""
@@ -1321,11 +1321,7 @@ def test_paired_launches_are_bit_identical_to_separate_ones(gpu):
             out = [dict(), dict()]
 
             def stage(fn):
-                with hip_ops.paired(enabled=paired) as pr:
-                    for k in (0, 1):
-                        if k and paired:
-                            pr.second()
-                        fn(mix[k], out[k])
+                hip_ops.both(lambda k: fn(mix[k], out[k]), enabled=paired)
 
             def conv(m, o):
                 o["xc"] = hip_ops.gather_conv1d_fwd(m["xz"][..., :Din], m["cw"], m["cb"], row_index=m["idx"], ndir=ndir, silu=True)
@@ -1405,10 +1401,7 @@ def test_n_entry_points_run_incongruent_launches_one_by_one(gpu):
 
     x0 = torch.randn(3, 40, 256, device=gpu)
     x1 = torch.randn(5, 40, 256, device=gpu)
-    with hip_ops.paired() as pr:
-        a = hip_ops.colsum(x0.view(-1, 256))
-        pr.second()
-        b = hip_ops.colsum(x1.view(-1, 256))
+    a, b = hip_ops.both(lambda k: hip_ops.colsum((x0, x1)[k].view(-1, 256)))
     torch.cuda.synchronize()
     torch.testing.assert_close(a, x0.view(-1, 256).sum(0), rtol=1e-5, atol=1e-4)
     torch.testing.assert_close(b, x1.view(-1, 256).sum(0), rtol=1e-5, atol=1e-4)
@@ -1546,12 +1539,7 @@ def test_gemm_pair_is_bit_identical_to_two_launches(gpu):
     real = _lib.call_n
     _lib.call_n = lambda name, arr, st: (calls.append(name), real(name, arr, st))[1]
     try:
-        got = [None, None]
-        with hip_ops.paired() as pr:
-            for k in (0, 1):
-                if k:
-                    pr.second()
-                got[k] = (hip_ops.gemm(x[k], W[k]), hip_ops.gemm(dy[k], W[k], True, False), hip_ops.gemm(dy[k], x[k], False, False, out_dtype=torch.float32))
+        got = hip_ops.both(lambda k: (hip_ops.gemm(x[k], W[k]), hip_ops.gemm(dy[k], W[k], True, False), hip_ops.gemm(dy[k], x[k], False, False, out_dtype=torch.float32)))
     finally:
         _lib.call_n = real
     torch.cuda.synchronize()

@@ -34,12 +34,7 @@ def t_us(fn, reps=20):
 
 
 def pair(fn):
-    def run():
-        with hip_ops.paired() as pr:
-            fn(0)
-            pr.second()
-            fn(1)
-    return run
+    return lambda: hip_ops.both(fn)
 
 
 for B in [int(a) for a in sys.argv[1:]] or [1, 8, 32, 64]:
