@@ -1,9 +1,9 @@
 """ctypes binding of libdiffma_hip.so (the C ABI declared in include/diffma_hip.h).
 
-The ctypes Structures are generated from the header text itself, so the Python view of every args
-struct cannot drift from the C one.  There is deliberately NO fallback: if the shared library is
-missing or a call fails, the caller gets an exception (the product path never routes through the
-CPU oracle).
+The ctypes Structures, the constants (dtype and status codes, DM_FLAG_*, integer #defines) and every
+function's argtypes are generated from the header text itself, so the Python view cannot drift from
+the C one.  There is deliberately NO fallback: if the shared library is missing or a call fails, the
+caller gets an exception (the product path never routes through the CPU oracle).
 """
 from __future__ import annotations
 
@@ -18,25 +18,42 @@ HEADER = os.path.join(_ROOT, "include", "diffma_hip.h")
 # DIFFMA_HIP_LIB: developer override used to A/B two builds of the kernels in one GPU session (tools/ab.sh)
 LIB_PATH = os.environ.get("DIFFMA_HIP_LIB") or os.path.join(_HERE, "csrc", "libdiffma_hip.so")
 
-DM_F32, DM_BF16, DM_F16 = 0, 1, 2
-DM_FLAG_DELTA_SOFTPLUS = 1
-DM_FLAG_SILU = 2
-DM_FLAG_DOUT_PER_SEQ = 4
-DM_FLAG_A_SHARED = 8
-DM_FLAG_SCAN_SEQUENTIAL = 16
-DM_FLAG_SCAN_CHUNKED = 32
-DM_FLAG_OUT_ACCUMULATE = 64
-DM_FLAG_DELTA_ACTIVATED = 128
-DM_FLAG_DX_MERGED = 256
-DM_FLAG_PARTIAL_COMPACT = 512
-
 _SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _strip_comments(text: str) -> str:
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def _parse_constants(text: str):
+    """Return {name: int} for every enumerator (dm_status, dm_dtype, DM_FLAG_*) and every integer `#define` of the header
+    (the include guard has no value and is not one)."""
+    text = _strip_comments(text)
+    out = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
+        for item in body.split(","):
+            if item.strip():
+                name, value = item.split("=")
+                out[name.strip()] = int(value, 0)
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\w+)[ \t]*$", text, flags=re.M):
+        out[name] = int(value, 0)
+    return out
+
+
+def _ctype_of(decl: str):
+    """The ctypes type of one parameter declaration: any pointer is c_void_p, a scalar is its own type."""
+    if "*" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if not words or words[0] not in _SCALARS:
+        raise RuntimeError(f"cannot derive a ctypes type from {decl!r}")
+    return _SCALARS[words[0]]
 
 
 def _parse_structs(text: str):
     """Return {struct_name: [(field, ctype), ...]} for every `typedef struct { ... } name;`."""
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
+    text = _strip_comments(text)
     out = {}
     for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
         fields = []
@@ -50,61 +67,34 @@ def _parse_structs(text: str):
             base, rest = m.group(2), m.group(3)
             for item in rest.split(","):
                 item = item.strip()
-                is_ptr = item.startswith("*")
-                fname = item.lstrip("* ").strip()
-                if is_ptr:
-                    fields.append((fname, ctypes.c_void_p))
-                else:
-                    if base not in _SCALARS:
-                        raise RuntimeError(f"unknown scalar type {base!r} in {name}.{fname}")
-                    fields.append((fname, _SCALARS[base]))
+                fields.append((item.lstrip("* ").strip(), _ctype_of(f"{base} {item}")))
         out[name] = fields
     return out
 
 
 def _parse_functions(text: str):
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
+    text = _strip_comments(text)
     protos = re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(dm_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)
     return [(ret.strip(), name, args.strip()) for ret, name, args in protos]
+
+
+def _argtypes_of(args: str):
+    """The argtypes of a prototype's parameter list, from its text: `(void)` takes none."""
+    return [] if args in ("void", "") else [_ctype_of(a) for a in args.split(",")]
 
 
 with open(HEADER) as _f:
     _HEADER_TEXT = _f.read()
 
+CONSTANTS = _parse_constants(_HEADER_TEXT)        # DM_F32.., DM_OK / DM_ERR_*, DM_FLAG_*, DM_ABI_VERSION, DM_LN_ROWS_PER_BLOCK, ...
 STRUCT_FIELDS = _parse_structs(_HEADER_TEXT)
 FUNCTIONS = _parse_functions(_HEADER_TEXT)
 EXPORTED_SYMBOLS = [name for _, name, _ in FUNCTIONS]
+ARGTYPES = {name: _argtypes_of(args) for _, name, args in FUNCTIONS}
 
-
-def _make_struct(name):
-    return type(name, (ctypes.Structure,), {"_fields_": STRUCT_FIELDS[name]})
-
-
-dm_scan_fwd_args = _make_struct("dm_scan_fwd_args")
-dm_scan_bwd_args = _make_struct("dm_scan_bwd_args")
-dm_conv_fwd_args = _make_struct("dm_conv_fwd_args")
-dm_conv_bwd_args = _make_struct("dm_conv_bwd_args")
-dm_conv_xproj_fwd_args = _make_struct("dm_conv_xproj_fwd_args")
-dm_conv_xproj_bwd_args = _make_struct("dm_conv_xproj_bwd_args")
-dm_merge_args = _make_struct("dm_merge_args")
-dm_gate_bwd_args = _make_struct("dm_gate_bwd_args")
-dm_dtproj_args = _make_struct("dm_dtproj_args")
-dm_dtproj_bwd_args = _make_struct("dm_dtproj_bwd_args")
-dm_ln_mod_args = _make_struct("dm_ln_mod_args")
-dm_blend_args = _make_struct("dm_blend_args")
-dm_gate_head_args = _make_struct("dm_gate_head_args")
-dm_rmsnorm_merge_args = _make_struct("dm_rmsnorm_merge_args")
-dm_colsum_args = _make_struct("dm_colsum_args")
-dm_sum_partials_args = _make_struct("dm_sum_partials_args")
-dm_diffusion_step_args = _make_struct("dm_diffusion_step_args")
-dm_ssd_fwd_args = _make_struct("dm_ssd_fwd_args")
-dm_ssd_bwd_args = _make_struct("dm_ssd_bwd_args")
-dm_gemm_args = _make_struct("dm_gemm_args")
-dm_repack_args = _make_struct("dm_repack_args")
-dm_adamw_tensor = _make_struct("dm_adamw_tensor")
-dm_adamw_args = _make_struct("dm_adamw_args")
-dm_training_loss_args = _make_struct("dm_training_loss_args")
+# every constant and one ctypes.Structure per args struct, importable by its C name (from ._lib import DM_BF16, dm_gemm_args, ...)
+globals().update(CONSTANTS)
+globals().update({_name: type(_name, (ctypes.Structure,), {"_fields_": _fields}) for _name, _fields in STRUCT_FIELDS.items()})
 
 _lib = None
 _lock = threading.Lock()
@@ -135,24 +125,9 @@ def load():
         for ret, name, args in FUNCTIONS:
             fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype = ctypes.c_char_p if "char" in ret else ctypes.c_int
-            if args in ("void", ""):
-                fn.argtypes = []
-            elif name in ("dm_conv_nchunk", "dm_scan_bwd_group_channels", "dm_gather_conv1d_xproj_width_supported"):   # int -> int helpers
-                fn.argtypes = [ctypes.c_int]
-            elif name in ("dm_ssd_fwd_supported", "dm_ssd_bwd_supported"):
-                fn.argtypes = [ctypes.c_int] * 4
-            elif name == "dm_scan_bwd_launch_group_channels":
-                fn.argtypes = [ctypes.c_int] * 5
-            elif name in ("dm_gather_conv1d_xproj_supported", "dm_gather_conv1d_xproj_bwd_supported", "dm_dtproj_softplus_supported", "dm_dtproj_bwd_supported"):
-                fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
-            elif name in ("dm_gemm_supported", "dm_gemm_large_supported"):
-                fn.argtypes = [ctypes.c_int] * 7
-            elif name.endswith("_n"):                    # an array of n argument structs (several congruent launches in one)
-                fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-            else:
-                fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            fn.argtypes = ARGTYPES[name]
         got = lib.dm_abi_version()
-        want = int(re.search(r"#define\s+DM_ABI_VERSION\s+(\d+)", _HEADER_TEXT).group(1))
+        want = CONSTANTS["DM_ABI_VERSION"]
         if got != want:
             raise DiffmaHipError(f"libdiffma_hip.so ABI {got} != header ABI {want}; rebuild the library")
         _lib = lib

@@ -15,46 +15,10 @@ namespace dm {
 constexpr int LN_WAVES = 4;
 constexpr int LN_MAXE = 16;     // values per lane: C <= 64 * 16
 
-__device__ __forceinline__ float wave_sum(float v) { return wave_sum_dpp(v); }
-
 // element c of the logical row [x | x2]
 template <typename T>
 __device__ __forceinline__ const T* row_src(const T* x, const T* x2, int64_t r, int64_t x_sr, int64_t x2_sr, int C1, int c) {
     return (c < C1) ? x + r * x_sr + c : x2 + r * x2_sr + (c - C1);
-}
-
-template <typename T, int VEC>
-__device__ __forceinline__ void ld_vec(float (&dst)[VEC], const T* p) {
-    if constexpr (VEC == 4) {
-        if constexpr (sizeof(T) == 4) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-            dst[0] = q.x; dst[1] = q.y; dst[2] = q.z; dst[3] = q.w;
-        } else {
-            alignas(8) T tmp[4];
-            *reinterpret_cast<f32x2*>(tmp) = *reinterpret_cast<const f32x2*>(p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dst[j] = io<T>::ld(&tmp[j]);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) dst[j] = io<T>::ld(p + j);
-    }
-}
-template <typename T, int VEC>
-__device__ __forceinline__ void st_vec(T* p, const float (&src)[VEC]) {
-    if constexpr (VEC == 4) {
-        if constexpr (sizeof(T) == 4) {
-            *reinterpret_cast<f32x4*>(p) = (f32x4){src[0], src[1], src[2], src[3]};
-        } else {
-            alignas(8) T tmp[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) io<T>::st(&tmp[j], src[j]);
-            *reinterpret_cast<f32x2*>(p) = *reinterpret_cast<const f32x2*>(tmp);
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) io<T>::st(p + j, src[j]);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -80,7 +44,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void ln_mod_fwd_kernel(const dm_ln_m
 #pragma unroll
         for (int j = 0; j < VEC; ++j) s += v[it][j];
     }
-    const float mean = wave_sum(s) / (float)C;
+    const float mean = wave_sum_dpp(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -91,7 +55,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void ln_mod_fwd_kernel(const dm_ln_m
             q += dlt * dlt;
         }
     }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + p.eps);
+    const float rstd = rsqrtf(wave_sum_dpp(q) / (float)C + p.eps);
     if (lane == 0 && p.stats) { p.stats[2 * r] = mean; p.stats[2 * r + 1] = rstd; }
     const float mk = p.mask ? io<TM>::ld((const TM*)p.mask + r) : 1.f;
 #pragma unroll
@@ -197,7 +161,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void ln_mod_bwd_kernel(const dm_ln_m
                 for (int j = 0; j < VEC; ++j) { xh[it][j] = 0.f; dxh[it][j] = 0.f; }
             }
         }
-        const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+        const float m1 = wave_sum_dpp(s1) / (float)C, m2 = wave_sum_dpp(s2) / (float)C;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int c = (it * 64 + lane) * VEC;
@@ -302,7 +266,7 @@ __global__ __launch_bounds__(64 * LN_WAVES) void blend_bwd_kernel(const dm_blend
                 st_vec<TS, VEC>((TS*)p.dws + r * p.C + c, o2);
             }
         }
-        sa = wave_sum(sa);
+        sa = wave_sum_dpp(sa);
         if (lane == 0) io<TS>::st((TS*)p.da + r, sa);
     }
 #pragma unroll
@@ -411,9 +375,7 @@ static int ln_entry(const dm_ln_mod_args* args, void* stream, bool bwd) {
     else if (a.x_dtype == DM_F16 && a.y_dtype == DM_F16) rc = ln_by_mod<f16_t, f16_t>(a, st, bwd);
     else { set_error("%s: unsupported (x_dtype, y_dtype) = (%d, %d)", who, a.x_dtype, a.y_dtype); return DM_ERR_DTYPE; }
     if (rc != DM_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status(who);
 }
 
 template <typename TX, typename TS, typename TG>
@@ -455,9 +417,7 @@ static int blend_entry(const dm_blend_args* args, void* stream, bool bwd) {
         default: set_error("%s: unsupported dtype triple (%d,%d,%d)", who, a.x_dtype, a.s_dtype, a.g_dtype); return DM_ERR_DTYPE;
     }
     if (rc != DM_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status(who);
 }
 
 }  // namespace dm

@@ -10,7 +10,7 @@
 // window through registers.  Algorithmic bytes: read x once per direction + write out = 2*s B/element
 // per direction (halo re-reads of W-1 rows per chunk are L2 hits).
 #include <initializer_list>
-#include "dm_common.h"
+#include "dm_mfma.h"
 
 namespace dm {
 
@@ -24,31 +24,9 @@ template <typename T> struct vio<T, 1> {
     static __device__ __forceinline__ void ld(const T* p, float (&v)[1]) { v[0] = io<T>::ld(p); }
     static __device__ __forceinline__ void st(T* p, const float (&v)[1]) { io<T>::st(p, v[0]); }
 };
-template <> struct vio<bf16_t, 2> {
-    static __device__ __forceinline__ void ld(const bf16_t* p, float (&v)[2]) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-        v[0] = __uint_as_float(w << 16);
-        v[1] = __uint_as_float(w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ void st(bf16_t* p, const float (&v)[2]) {
-        uint32_t w;
-        w = dm_cvt_pk_bf16(v[0], v[1]);
-        *reinterpret_cast<uint32_t*>(p) = w;
-    }
-};
-template <> struct vio<f16_t, 2> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ void ld(const f16_t* p, float (&v)[2]) {
-        const h2 w = *reinterpret_cast<const h2*>(p);
-        v[0] = (float)w.x;
-        v[1] = (float)w.y;
-    }
-    static __device__ __forceinline__ void st(f16_t* p, const float (&v)[2]) {
-        h2 w;
-        w.x = (_Float16)v[0];
-        w.y = (_Float16)v[1];
-        *reinterpret_cast<h2*>(p) = w;
-    }
+template <typename T> struct vio<T, 2> {          // 16-bit T: the pair pack / unpack of dm_mfma.h
+    static __device__ __forceinline__ void ld(const T* p, float (&v)[2]) { mfma<T>::unpack(*reinterpret_cast<const uint32_t*>(p), v[0], v[1]); }
+    static __device__ __forceinline__ void st(T* p, const float (&v)[2]) { *reinterpret_cast<uint32_t*>(p) = mfma<T>::pack(v[0], v[1]); }
 };
 
 template <typename T, typename TW, int W, bool SILU, int VEC>
@@ -271,9 +249,7 @@ static int launch_conv_fwd(const dm_conv_fwd_args& a, const dm_conv_fwd_args* se
     } else {
         launch_conv_fwd_v<T, TW, W, 1>(a, second, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gather_conv1d_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gather_conv1d_fwd");
 }
 
 template <typename T, typename TW, int W, int VEC>
@@ -297,9 +273,7 @@ static int launch_conv_bwd(const dm_conv_bwd_args& a, const dm_conv_bwd_args* se
     } else {
         launch_conv_bwd_v<T, TW, W, 1>(a, second, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gather_conv1d_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gather_conv1d_bwd");
 }
 
 template <typename T, typename TW, typename Args, int (*F2)(const Args&, const Args*, hipStream_t),

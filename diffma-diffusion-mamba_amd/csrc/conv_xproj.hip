@@ -17,50 +17,13 @@
 // x, write x~) + the x_dbl rows.
 #include <cstdlib>
 #include <type_traits>
-#include "dm_common.h"
+#include "dm_mfma.h"
 
 namespace dm {
 
 constexpr int XP_TM = 16;                 // rows per tile (MFMA M)
 constexpr int XP_THREADS = 512;           // 8 waves: wave w owns output columns 16*(w&3).. and the K half (w>>2)
 constexpr int XP_PAD = 8;                 // tile row padding in elements (16 B): spreads the 16 rows of an A-fragment read over the banks
-
-typedef __bf16 xp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 xp_f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t xp_u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct xp_mfma;
-template <> struct xp_mfma<bf16_t> {
-    static __device__ __forceinline__ f32x4 run(const xp_u32x4& a, const xp_u32x4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(xp_bf16x8, a), __builtin_bit_cast(xp_bf16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        uint32_t r;
-        r = dm_cvt_pk_bf16(lo, hi);                      // (through the compiler: -3 % K3x, -5 % K4x against the inline-asm form)
-        return r;
-    }
-    static __device__ __forceinline__ void unpack(uint32_t w, float& lo, float& hi) {
-        lo = __uint_as_float(w << 16);
-        hi = __uint_as_float(w & 0xffff0000u);
-    }
-};
-template <> struct xp_mfma<f16_t> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ f32x4 run(const xp_u32x4& a, const xp_u32x4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(xp_f16x8, a), __builtin_bit_cast(xp_f16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        h2 v;
-        v.x = (_Float16)lo;
-        v.y = (_Float16)hi;
-        return __builtin_bit_cast(uint32_t, v);
-    }
-    static __device__ __forceinline__ void unpack(uint32_t w, float& lo, float& hi) {
-        const h2 v = __builtin_bit_cast(h2, w);
-        lo = (float)v.x;
-        hi = (float)v.y;
-    }
-};
 
 // KSTEPS = dim / 32 (MFMA K steps, even).  Thread t owns channels 2t, 2t+1 (dim <= 1024).
 template <typename T, typename TW, int W, bool SILU, int KSTEPS, bool IDX>
@@ -100,13 +63,13 @@ __global__ __launch_bounds__(XP_THREADS, 4) void conv_xproj_fwd_kernel(const dm_
     const int ncol = p.nproj;
     const int col = nt * 16 + ij;
     const bool wave_on = nt * 16 < ncol;                             // wave-uniform
-    xp_u32x4 bfrag[KH];
+    u32x4_t bfrag[KH];
     {   // a bounded descriptor: columns >= nproj read as zero, no branches
         const rsrc_t r_wx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wx), 0, ncol * D * (int)sizeof(T), 0x00020000);
 #pragma unroll
         for (int kk = 0; kk < KH; ++kk) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(r_wx, (col * D + (kh * KH + kk) * 32 + g * 8) * (int)sizeof(T), 0, 0);
-            bfrag[kk] = (xp_u32x4){q[0], q[1], q[2], q[3]};
+            bfrag[kk] = (u32x4_t){q[0], q[1], q[2], q[3]};
         }
     }
 
@@ -144,7 +107,7 @@ __global__ __launch_bounds__(XP_THREADS, 4) void conv_xproj_fwd_kernel(const dm_
         for (int j = h * (XP_TM / 2); j < (h + 1) * (XP_TM / 2); ++j) {
             const bool valid = l0 + j < L;                            // wave-uniform
             float xv[2], acc[2];
-            xp_mfma<T>::unpack(xin[j], xv[0], xv[1]);
+            mfma<T>::unpack(xin[j], xv[0], xv[1]);
 #pragma unroll
             for (int v = 0; v < 2; ++v) {
                 acc[v] = bias[v];                                     // same summation order as conv_fwd_kernel: bit-identical x~
@@ -156,7 +119,7 @@ __global__ __launch_bounds__(XP_THREADS, 4) void conv_xproj_fwd_kernel(const dm_
                 for (int k = 0; k < W - 2; ++k) win[k][v] = win[k + 1][v];
                 if (W > 1) win[W - 2][v] = xv[v];
             }
-            const uint32_t pk = valid ? xp_mfma<T>::pack(acc[0], acc[1]) : 0u;
+            const uint32_t pk = valid ? mfma<T>::pack(acc[0], acc[1]) : 0u;
             if (act) {
                 *reinterpret_cast<uint32_t*>(tl + j * ROW + c) = pk;               // the A tile the matrix pipe reads (16-bit, rounded like x~)
                 if (valid) __builtin_amdgcn_raw_buffer_store_b32(pk, r_o, vo, (l0 + j) * sl_o, 0);
@@ -174,8 +137,8 @@ __global__ __launch_bounds__(XP_THREADS, 4) void conv_xproj_fwd_kernel(const dm_
         if (wave_on) {
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk) {
-                const xp_u32x4 a = *reinterpret_cast<const xp_u32x4*>(tl + ij * ROW + (kh * KH + kk) * 32 + g * 8);   // A[i = ij][k .. k+7]
-                acc = xp_mfma<T>::run(a, bfrag[kk], acc);
+                const u32x4_t a = *reinterpret_cast<const u32x4_t*>(tl + ij * ROW + (kh * KH + kk) * 32 + g * 8);   // A[i = ij][k .. k+7]
+                acc = mfma<T>::m16(a, bfrag[kk], acc);
             }
             if (kh == 1) red[nt][lane] = acc;
         }
@@ -215,9 +178,7 @@ static int xp_by_dim(const dm_conv_xproj_fwd_args& a, hipStream_t st) {
         case 128: launch_xp<T, TW, W, 4>(a, st); break;
         default: set_error("dm_gather_conv1d_xproj_fwd: dim %d not instantiated (128, 256, 512, 1024)", a.dim); return DM_ERR_ARG;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gather_conv1d_xproj_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gather_conv1d_xproj_fwd");
 }
 
 template <typename T, typename TW>
@@ -311,14 +272,14 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
 
     // x_proj.weight^T rows of this wave's channels as B-fragments, resident for the whole sequence:
     // B[k][j] = Wx[k][ch] = wxt[ch][k]; lane (g, j) holds wxt[(wave*NTW + n)*16 + j][32 kk + 8g .. +7]
-    xp_u32x4 bfrag[NTW][2];
+    u32x4_t bfrag[NTW][2];
 #pragma unroll
     for (int n = 0; n < NTW; ++n) {
         const int ch = (wave * NTW + n) * 16 + ij;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(r_wt, (ch * KP + 32 * kk + 8 * g) * ES, 0, 0);
-            bfrag[n][kk] = (xp_u32x4){q[0], q[1], q[2], q[3]};
+            bfrag[n][kk] = (u32x4_t){q[0], q[1], q[2], q[3]};
         }
     }
 
@@ -374,13 +335,13 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
         }
     };
     // dx_dbl rows of a tile as A-fragments: lane (g, i) holds dx_dbl[l0 + i][32 kk + 8g .. +7]; rows past L read row L-1 and are zeroed
-    auto load_a = [&](int l0, xp_u32x4(&af)[2]) {
+    auto load_a = [&](int l0, u32x4_t(&af)[2]) {
         const int lr = l0 + ij;
         const int l = lr < L ? lr : L - 1;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(r_xd, l * sr_xd + (32 * kk + 8 * g) * ES, 0, 0);
-            af[kk] = (lr < L) ? (xp_u32x4){q[0], q[1], q[2], q[3]} : (xp_u32x4){0u, 0u, 0u, 0u};
+            af[kk] = (lr < L) ? (u32x4_t){q[0], q[1], q[2], q[3]} : (u32x4_t){0u, 0u, 0u, 0u};
         }
     };
     // the running sum's rows of a half tile (MERGED, directions after the first), requested with the du rows half a tile ahead;
@@ -397,7 +358,7 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
         }
     };
     uint32_t xr[NXR], xn[NXR], dur[XP_TM];
-    xp_u32x4 afrag[2], anext[2];
+    u32x4_t afrag[2], anext[2];
     load_a((ntile - 1) * XP_TM, afrag);
     load_x((ntile - 1) * XP_TM, xr);
     load_du_half((ntile - 1) * XP_TM, 0, dur);
@@ -413,8 +374,8 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
 #pragma unroll
         for (int n = 0; n < NTW; ++n) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = xp_mfma<T>::run(afrag[0], bfrag[n][0], acc);
-            acc = xp_mfma<T>::run(afrag[1], bfrag[n][1], acc);
+            acc = mfma<T>::m16(afrag[0], bfrag[n][0], acc);
+            acc = mfma<T>::m16(afrag[1], bfrag[n][1], acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) ptile[(4 * g + r) * ROWP + (wave * NTW + n) * 16 + ij] = acc[r];
         }
@@ -432,10 +393,10 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
                 const bool valid = l < L;                              // wave-uniform
                 const f32x2 pv = *reinterpret_cast<const f32x2*>(&ptile[j * ROWP + c]);
                 float duv[2], xw[W][2];
-                xp_mfma<T>::unpack(dur[j], duv[0], duv[1]);
+                mfma<T>::unpack(dur[j], duv[0], duv[1]);
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
-                    xp_mfma<T>::unpack(xr[j + k], xw[k][0], xw[k][1]);
+                    mfma<T>::unpack(xr[j + k], xw[k][0], xw[k][1]);
                     if (l - (W - 1) + k < 0) { xw[k][0] = 0.0f; xw[k][1] = 0.0f; }
                 }
                 float gv[2], dxv[2];
@@ -463,11 +424,11 @@ __global__ __launch_bounds__(XP_THREADS, 2) void conv_xproj_bwd_kernel(const dm_
                     const int r = IDX ? idx[l] : l;
                     if (MERGED && accum) {
                         float o0, o1;
-                        xp_mfma<T>::unpack(dold[j], o0, o1);
+                        mfma<T>::unpack(dold[j], o0, o1);
                         dxv[0] += o0;
                         dxv[1] += o1;
                     }
-                    __builtin_amdgcn_raw_buffer_store_b32(xp_mfma<T>::pack(dxv[0], dxv[1]), r_dx, vo, r * sl_dx, 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(mfma<T>::pack(dxv[0], dxv[1]), r_dx, vo, r * sl_dx, 0);
                 }
             }
             if (t > 0) {
@@ -544,7 +505,7 @@ __device__ __forceinline__ int64_t xs_uniform64(int64_t v) {      // a wave-unif
 template <typename T, int RT> struct xs_bufs {     // one tile's prefetched rows
     uint32_t x[RT + 3];                    // x rows l0-3 .. l0+RT-1 (gathered), the lane's channel pair
     uint32_t du[RT];
-    xp_u32x4 a[2];                         // d x_dbl rows l0 .. l0+15 as MFMA A-fragments
+    u32x4_t a[2];                         // d x_dbl rows l0 .. l0+15 as MFMA A-fragments
 };
 
 // RT: rows of a tile the conv walks (the product tile always has the 16 rows of the MFMA): 16, or 14 when that wastes fewer row
@@ -564,7 +525,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
     static_assert(RT % 2 == 0 && RT <= XP_TM, "whole half tiles");
     __shared__ __attribute__((aligned(16))) uint32_t accs[(XS_MAXL + 1) * AW];
     __shared__ __attribute__((aligned(16))) float ptile[XS_NW][XP_TM * XS_ROWP];
-    __shared__ __attribute__((aligned(16))) xp_u32x4 bfl[NT * 2 * WAVE];          // x_proj.weight^T of the slab in MFMA B-fragment order
+    __shared__ __attribute__((aligned(16))) u32x4_t bfl[NT * 2 * WAVE];          // x_proj.weight^T of the slab in MFMA B-fragment order
     __shared__ __attribute__((aligned(8))) xs_row rowtab[XS_NW][XS_MAXDIR * XS_SLOTS];
     __shared__ uint8_t xtok[XS_MAXDIR][XS_TOKP];                                  // token of gathered row l at [dir][l + 3], l = -3 .. (clamped into the sequence)
 
@@ -578,8 +539,8 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
     if (b_first >= p.batch) return;                                               // (workgroup-uniform: before any barrier)
     const int c0 = slab * XS_CS, c = c0 + 2 * lane;
     {   // the running sum starts at zero: direction 0 adds like the others
-        const xp_u32x4 z = {0u, 0u, 0u, 0u};
-        for (int q = tid; q < L * (AW / 4); q += XS_THREADS) reinterpret_cast<xp_u32x4*>(accs)[q] = z;
+        const u32x4_t z = {0u, 0u, 0u, 0u};
+        for (int q = tid; q < L * (AW / 4); q += XS_THREADS) reinterpret_cast<u32x4_t*>(accs)[q] = z;
     }
     for (int q = tid; q < p.ndir * XS_TOKP; q += XS_THREADS) {
         const int dir = q / XS_TOKP, lr = q % XS_TOKP - (W - 1);
@@ -595,7 +556,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
         const auto q = __builtin_amdgcn_raw_buffer_load_b128(r_wt, ((wave * 16 + ij) * KP + 32 * kk + 8 * g) * ES, 0, 0);
-        bfl[(wave * 2 + kk) * WAVE + lane] = (xp_u32x4){q[0], q[1], q[2], q[3]};
+        bfl[(wave * 2 + kk) * WAVE + lane] = (u32x4_t){q[0], q[1], q[2], q[3]};
     }
     f32x2 w[W], bias, dw[W], db, gnext[W - 1];            // gnext[k] = gradient of row (end of the half in work) + k: the rows done before
 #pragma unroll
@@ -641,7 +602,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const auto q = __builtin_amdgcn_raw_buffer_load_b128(r_xd, (l0 + ij) * sr_xd + (32 * kk + 8 * g) * ES + (live ? 0 : BIO_OOB), 0, 0);   // (a sum: a select on the uniform flag becomes a branch)
-            o.a[kk] = (xp_u32x4){q[0], q[1], q[2], q[3]};
+            o.a[kk] = (u32x4_t){q[0], q[1], q[2], q[3]};
         }
 #pragma unroll
         for (int j = NXR - 1; j >= 0; --j) o.x[j] = __builtin_amdgcn_raw_buffer_load_b32(r_x, vo_l, __builtin_amdgcn_readlane(tokv, j) * sl_x, 0);
@@ -672,8 +633,8 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            acc = xp_mfma<T>::run(cur.a[0], bfl[(n * 2) * WAVE + lane], acc);
-            acc = xp_mfma<T>::run(cur.a[1], bfl[(n * 2 + 1) * WAVE + lane], acc);
+            acc = mfma<T>::m16(cur.a[0], bfl[(n * 2) * WAVE + lane], acc);
+            acc = mfma<T>::m16(cur.a[1], bfl[(n * 2 + 1) * WAVE + lane], acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) pt[(4 * g + r) * XS_ROWP + n * 16 + ij] = acc[r];
         }
@@ -724,7 +685,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
 #pragma unroll
                 for (int k = 0; k < W - 1; ++k) dxv += w[W - 2 - k] * gv[jj + 1 + k];
                 const f32x2 o = xs_pair<T>::up(old[jj]) + dxv;
-                *ap[jj] = xp_mfma<T>::pack(o.x, o.y);
+                *ap[jj] = mfma<T>::pack(o.x, o.y);
             }
         }
         if (t == 0) {
@@ -733,9 +694,9 @@ __global__ __launch_bounds__(XS_THREADS, 1) void conv_xproj_bwd_slab_kernel(cons
                 const rsrc_t r_dx = make_rsrc((T*)p.dx + xs_uniform64((int64_t)bb * p.dx_ss + c0));
                 const int sl_dx = (int)p.dx_sl * ES;
                 const int piece = tid & 15;
-                const xp_u32x4 z = {0u, 0u, 0u, 0u};
+                const u32x4_t z = {0u, 0u, 0u, 0u};
                 for (int r = tid >> 4; r < L; r += XS_THREADS / 16) {
-                    xp_u32x4* const q = reinterpret_cast<xp_u32x4*>(accs + r * AW + 4 * piece);
+                    u32x4_t* const q = reinterpret_cast<u32x4_t*>(accs + r * AW + 4 * piece);
                     __builtin_amdgcn_raw_buffer_store_b128(*q, r_dx, piece * 16 + r * sl_dx, 0, 0);      // (the row differs inside a wave: lane offset)
                     *q = z;
                 }
@@ -868,9 +829,7 @@ static int xpb_by_dim(const dm_conv_xproj_bwd_args& a, hipStream_t st) {
         case 128: launch_xpb<T, TW, W, 128>(a, st); break;
         default: set_error("dm_gather_conv1d_xproj_bwd: dim %d not instantiated (128, 256, 512, 1024)", a.dim); return DM_ERR_ARG;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gather_conv1d_xproj_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gather_conv1d_xproj_bwd");
 }
 
 template <typename T, typename TW>

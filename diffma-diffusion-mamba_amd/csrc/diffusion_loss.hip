@@ -154,9 +154,7 @@ extern "C" int dm_q_sample(const dm_training_loss_args* args, void* stream) {
     const int64_t total = (int64_t)a.batch * a.channels * a.hw;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(q_sample_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_q_sample: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_q_sample");
 }
 
 extern "C" int dm_training_loss(const dm_training_loss_args* args, void* stream) {
@@ -173,9 +171,7 @@ extern "C" int dm_training_loss(const dm_training_loss_args* args, void* stream)
         case DM_F16: hipLaunchKernelGGL((training_loss_kernel<f16_t>), dim3(a.batch), dim3(DL_THREADS), 0, st, a); break;
         default: set_error("dm_training_loss: bad out_dtype %d", a.out_dtype); return DM_ERR_DTYPE;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_training_loss: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_training_loss");
 }
 
 extern "C" int dm_training_loss_bwd(const dm_training_loss_args* args, void* stream) {
@@ -193,7 +189,5 @@ extern "C" int dm_training_loss_bwd(const dm_training_loss_args* args, void* str
         case DM_F16: hipLaunchKernelGGL((training_loss_bwd_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, a); break;
         default: set_error("dm_training_loss_bwd: bad out_dtype %d", a.out_dtype); return DM_ERR_DTYPE;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_training_loss_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_training_loss_bwd");
 }

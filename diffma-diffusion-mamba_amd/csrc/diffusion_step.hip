@@ -68,7 +68,5 @@ extern "C" int dm_diffusion_step(const dm_diffusion_step_args* args, void* strea
         case DM_F16: hipLaunchKernelGGL((diffusion_step_kernel<f16_t>), dim3(blocks), dim3(256), 0, st, a); break;
         default: set_error("dm_diffusion_step: bad out_dtype %d", a.out_dtype); return DM_ERR_DTYPE;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_diffusion_step: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_diffusion_step");
 }

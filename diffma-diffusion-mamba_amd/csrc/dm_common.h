@@ -30,6 +30,13 @@ template <typename A> struct mix_args {
 //                       code path that takes one struct only has no `second` parameter.
 // The single entry point is null check, check, run(a, nullptr, st); the dm_*_n entry point is mix_run_n.
 void set_error(const char* fmt, ...);        // thread-local error string (capi.hip)
+// the tail of every launching entry point: DM_OK, or DM_ERR_LAUNCH with the runtime's reason if the launch just made was refused
+static inline int launch_status(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return DM_OK;
+    set_error("%s: launch failed: %s", who, hipGetErrorString(e));
+    return DM_ERR_LAUNCH;
+}
 template <typename A> static inline mix_args<A> mix_make(const A& a, const A* second, unsigned& gz) {
     mix_args<A> m;
     m.a[0] = a;
@@ -250,6 +257,33 @@ __device__ __forceinline__ void bio_ld_vec(float (&v)[NS], rsrc_t r, int voff, i
     } else {
 #pragma unroll
         for (int k = 0; k < NS; ++k) v[k] = bio<T>::ld(r, voff + k * (int)sizeof(T), soff);
+    }
+}
+
+// VEC consecutive elements of a row in memory, widened to fp32 / narrowed from it: one 16-byte or 8-byte access where VEC * sizeof(T)
+// is that (p aligned to it), element accesses otherwise
+template <typename T, int VEC>
+__device__ __forceinline__ void ld_vec(float (&dst)[VEC], const T* p) {
+    alignas(16) T tmp[VEC];
+    if constexpr (VEC * sizeof(T) == 16) *(f32x4*)tmp = *(const f32x4*)p;
+    else if constexpr (VEC * sizeof(T) == 8) *(f32x2*)tmp = *(const f32x2*)p;
+    else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) tmp[j] = p[j];
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) dst[j] = io<T>::ld(&tmp[j]);
+}
+template <typename T, int VEC>
+__device__ __forceinline__ void st_vec(T* p, const float (&src)[VEC]) {
+    alignas(16) T tmp[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) io<T>::st(&tmp[j], src[j]);
+    if constexpr (VEC * sizeof(T) == 16) *(f32x4*)p = *(const f32x4*)tmp;
+    else if constexpr (VEC * sizeof(T) == 8) *(f32x2*)p = *(const f32x2*)tmp;
+    else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) p[j] = tmp[j];
     }
 }
 

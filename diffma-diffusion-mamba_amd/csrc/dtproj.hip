@@ -13,9 +13,8 @@
 //   1536 sequences: 179 us against 218 us for direct 16-byte stores from the accumulator layout and 184 us for 64-byte
 //   pieces per row; two quads per wave: 192 us).  Weight fragments and the bias stay in registers for all row tiles of the
 //   workgroup.  The write of delta (616 MB at that shape) is the floor: the library GEMM without the softplus takes 143-149 us.
-#include "dm_common.h"
+#include "dm_mfma.h"
 #include <cstdlib>
-#include <type_traits>
 
 namespace dm {
 
@@ -23,33 +22,8 @@ constexpr int DTP_WAVES = 4;      // waves per workgroup
 constexpr int DTP_TILES = 8;      // row tiles (16 rows) per workgroup
 constexpr int DTP_NQ = 1;         // quads (64 columns) per wave -> 256 columns per workgroup (grid.y covers dim)
 
-typedef __bf16 dtp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 dtp_f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t dtp_u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct dtp_mfma;
-template <> struct dtp_mfma<bf16_t> {
-    static __device__ __forceinline__ f32x4 run(const dtp_u32x4& a, const dtp_u32x4& b) {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dtp_bf16x8, a), __builtin_bit_cast(dtp_bf16x8, b), z, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) { return dm_cvt_pk_bf16(lo, hi); }
-};
-template <> struct dtp_mfma<f16_t> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ f32x4 run(const dtp_u32x4& a, const dtp_u32x4& b) {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dtp_f16x8, a), __builtin_bit_cast(dtp_f16x8, b), z, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        h2 v;
-        v.x = (_Float16)lo;
-        v.y = (_Float16)hi;
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 // softplus for a 16-bit result: below e = 2^-12 log(1 + e) = e to 2^-13 relative, far inside the output rounding
+// (separate from softplus_f, which keeps the second term of the log1p series because its results stay fp32)
 __device__ __forceinline__ float softplus16_f(float x) {
     const float e = fast_exp2(x * LOG2E);
     const float big = fast_log2(1.0f + e) * LN2;
@@ -74,15 +48,15 @@ __global__ __launch_bounds__(64 * DTP_WAVES) void dtproj_softplus_kernel(const m
 
     // weight fragments: tile t of quad q, row i of the tile = output column cb + q*64 + (i>>2)*16 + t*4 + (i&3)
     auto colmap = [](int gg, int t, int r) { return gg * 16 + t * 4 + r; };
-    dtp_u32x4 wf[DTP_NQ][4];
+    u32x4_t wf[DTP_NQ][4];
     float bias[DTP_NQ][16];
 #pragma unroll
     for (int q = 0; q < DTP_NQ; ++q) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int col = cb + q * 64 + colmap(j >> 2, t, j & 3);
-            wf[q][t] = (dtp_u32x4){0u, 0u, 0u, 0u};
-            if (kvalid && col < p.dim) wf[q][t] = *reinterpret_cast<const dtp_u32x4*>(W + (int64_t)col * R + 8 * g);
+            wf[q][t] = (u32x4_t){0u, 0u, 0u, 0u};
+            if (kvalid && col < p.dim) wf[q][t] = *reinterpret_cast<const u32x4_t*>(W + (int64_t)col * R + 8 * g);
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -95,37 +69,37 @@ __global__ __launch_bounds__(64 * DTP_WAVES) void dtproj_softplus_kernel(const m
     // per GPU: 37 tiles per mixer) is spread over more workgroups instead of walking 8 tiles one after the other in 20 of them
     const int tpw = (((p.rows + 15) >> 4) + (int)gridDim.x - 1) / (int)gridDim.x;
     const int tile0 = blockIdx.x * tpw;
-    auto load_x = [&](int tile) -> dtp_u32x4 {
+    auto load_x = [&](int tile) -> u32x4_t {
         int m = tile * 16 + j;
         m = (m < p.rows) ? m : p.rows - 1;
-        dtp_u32x4 v = {0u, 0u, 0u, 0u};
-        if (kvalid) v = *reinterpret_cast<const dtp_u32x4*>(X + (int64_t)m * p.xd_sr + 8 * g);
+        u32x4_t v = {0u, 0u, 0u, 0u};
+        if (kvalid) v = *reinterpret_cast<const u32x4_t*>(X + (int64_t)m * p.xd_sr + 8 * g);
         return v;
     };
-    dtp_u32x4 xf = load_x(tile0);
+    u32x4_t xf = load_x(tile0);
 #pragma unroll 1
     for (int tt = 0; tt < tpw; ++tt) {
         const int tile = tile0 + tt;
         if (tile * 16 >= p.rows) break;                                        // wave-uniform
-        const dtp_u32x4 xcur = xf;
+        const u32x4_t xcur = xf;
         if (tt + 1 < tpw) xf = load_x(tile + 1);                                // clamped rows: always a legal address
 #pragma unroll
         for (int q = 0; q < DTP_NQ; ++q) {
             uint32_t pk[8];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const f32x4 acc = dtp_mfma<T>::run(wf[q][t], xcur);
+                const f32x4 acc = mfma<T>::m16(wf[q][t], xcur, (f32x4){0.f, 0.f, 0.f, 0.f});
                 const float v0 = softplus16_f(acc[0] + bias[q][4 * t + 0]);
                 const float v1 = softplus16_f(acc[1] + bias[q][4 * t + 1]);
                 const float v2 = softplus16_f(acc[2] + bias[q][4 * t + 2]);
                 const float v3 = softplus16_f(acc[3] + bias[q][4 * t + 3]);
-                pk[2 * t] = dtp_mfma<T>::pack(v0, v1);
-                pk[2 * t + 1] = dtp_mfma<T>::pack(v2, v3);
+                pk[2 * t] = mfma<T>::pack(v0, v1);
+                pk[2 * t + 1] = mfma<T>::pack(v2, v3);
             }
             {
                 T* const srow = &stage[wave][j][q * 64 + g * 16];
-                *reinterpret_cast<dtp_u32x4*>(srow) = (dtp_u32x4){pk[0], pk[1], pk[2], pk[3]};
-                *reinterpret_cast<dtp_u32x4*>(srow + 8) = (dtp_u32x4){pk[4], pk[5], pk[6], pk[7]};
+                *reinterpret_cast<u32x4_t*>(srow) = (u32x4_t){pk[0], pk[1], pk[2], pk[3]};
+                *reinterpret_cast<u32x4_t*>(srow + 8) = (u32x4_t){pk[4], pk[5], pk[6], pk[7]};
             }
         }
         {                                                                      // wave-private tile: no barrier, LDS ops of a wave are ordered
@@ -134,9 +108,9 @@ __global__ __launch_bounds__(64 * DTP_WAVES) void dtproj_softplus_kernel(const m
 #pragma unroll
             for (int s0 = 0; s0 < 16; s0 += ROWS_PER) {
                 const int rr = s0 + lane / PIECES, pc = lane % PIECES;
-                const dtp_u32x4 v = *reinterpret_cast<const dtp_u32x4*>(&stage[wave][rr][pc * 8]);
+                const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&stage[wave][rr][pc * 8]);
                 const int mm = tile * 16 + rr, cc = cb + pc * 8;
-                if (mm < p.rows && cc < p.dim) *reinterpret_cast<dtp_u32x4*>(O + (int64_t)mm * p.dim + cc) = v;
+                if (mm < p.rows && cc < p.dim) *reinterpret_cast<u32x4_t*>(O + (int64_t)mm * p.dim + cc) = v;
             }
         }
     }
@@ -166,9 +140,7 @@ static int run_dtproj_fwd(const dm_dtproj_args& a, const dm_dtproj_args* second,
     for (int tpw = DTP_TILES / 2; tpw >= 1 && grid.x * grid.y * gz < 512; tpw /= 2) grid.x = (tiles + tpw - 1) / tpw;     // fewer tiles per workgroup until the chip is covered twice
     if (a.io_dtype == DM_BF16) hipLaunchKernelGGL((dtproj_softplus_kernel<bf16_t>), grid, dim3(64 * DTP_WAVES), 0, st, m);
     else hipLaunchKernelGGL((dtproj_softplus_kernel<f16_t>), grid, dim3(64 * DTP_WAVES), 0, st, m);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_dtproj_softplus_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_dtproj_softplus_fwd");
 }
 
 }  // namespace dm
@@ -228,7 +200,7 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
     T* __restrict__ O = (T*)p.dxdbl;
 
     // W fragments (operand A of product 1): lane (j, g) of tile (kc, nr) holds W[d0 + 32 kc + 8 g .. + 8][16 nr + j]
-    dtp_u32x4 wf[KC][NR];
+    u32x4_t wf[KC][NR];
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
 #pragma unroll
@@ -240,7 +212,7 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
                 const uint32_t lo = __builtin_bit_cast(unsigned short, src[0]), hi = __builtin_bit_cast(unsigned short, src[R]);
                 w[e] = lo | (hi << 16);
             }
-            wf[kc][nr] = (dtp_u32x4){w[0], w[1], w[2], w[3]};
+            wf[kc][nr] = (u32x4_t){w[0], w[1], w[2], w[3]};
         }
     }
     f32x4 accw[NR][2 * KC];                        // dW^T tiles: rows = r (16 nr + 4 g + i), column = channel d0 + 16 nt + j
@@ -251,19 +223,19 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
 
     const int ntile = (p.rows + DTB_TM - 1) / DTB_TM;             // the last tile may be ragged: its rows past the end read row rows-1 and are zeroed at use
     // fragments of a tile: [m-tile of 16 rows][kc]: lane (j, g) holds dd[tile*32 + 16 mt + j][d0 + 32 kc + 8 g .. + 8]
-    auto load_tile = [&](int t, dtp_u32x4(&f)[2][KC], dtp_u32x4& xv) {
+    auto load_tile = [&](int t, u32x4_t(&f)[2][KC], u32x4_t& xv) {
         t = (t < ntile) ? t : ntile - 1;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc)
-                f[mt][kc] = *reinterpret_cast<const dtp_u32x4*>(DD + (int64_t)min(t * DTB_TM + 16 * mt + j, p.rows - 1) * DIM + d0 + 32 * kc + 8 * g);
+                f[mt][kc] = *reinterpret_cast<const u32x4_t*>(DD + (int64_t)min(t * DTB_TM + 16 * mt + j, p.rows - 1) * DIM + d0 + 32 * kc + 8 * g);
         // the xdt tile [32][R] is R/8 16-byte pieces per row: the first 32 * R / 8 threads of the workgroup fetch one each
         const int pr = tid / (R / 8), pc = tid % (R / 8);
-        xv = (dtp_u32x4){0u, 0u, 0u, 0u};
-        if (pr < DTB_TM) xv = *reinterpret_cast<const dtp_u32x4*>(X + (int64_t)min(t * DTB_TM + pr, p.rows - 1) * p.xd_sr + 8 * pc);
+        xv = (u32x4_t){0u, 0u, 0u, 0u};
+        if (pr < DTB_TM) xv = *reinterpret_cast<const u32x4_t*>(X + (int64_t)min(t * DTB_TM + pr, p.rows - 1) * p.xd_sr + 8 * pc);
     };
-    dtp_u32x4 cur[2][KC], nxt[2][KC], xcur, xnxt;
+    u32x4_t cur[2][KC], nxt[2][KC], xcur, xnxt;
     load_tile(blockIdx.x, cur, xcur);
     for (int t = blockIdx.x; t < ntile; t += gridDim.x) {
         load_tile(t + gridDim.x, nxt, xnxt);                       // lands while this tile is multiplied (clamped: always a legal tile)
@@ -272,7 +244,7 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
             for (int mt = 0; mt < 2; ++mt)
                 if (t * DTB_TM + 16 * mt + j >= p.rows) {
 #pragma unroll
-                    for (int kc = 0; kc < KC; ++kc) cur[mt][kc] = (dtp_u32x4){0u, 0u, 0u, 0u};
+                    for (int kc = 0; kc < KC; ++kc) cur[mt][kc] = (u32x4_t){0u, 0u, 0u, 0u};
                 }
         }
         // ---- product 1, this wave's channel slice: acc[mt][nr] = W-fragment x dd-fragment, D[r][row]
@@ -284,10 +256,7 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
                 f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kc = 0; kc < KC; ++kc) {
-                    if constexpr (std::is_same<T, bf16_t>::value)
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dtp_bf16x8, wf[kc][nr]), __builtin_bit_cast(dtp_bf16x8, cur[mt][kc]), a, 0, 0, 0);
-                    else
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dtp_f16x8, wf[kc][nr]), __builtin_bit_cast(dtp_f16x8, cur[mt][kc]), a, 0, 0, 0);
+                    a = mfma<T>::m16(wf[kc][nr], cur[mt][kc], a);
                 }
                 acc1[mt][nr] = a;
             }
@@ -295,10 +264,10 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int kc = 0; kc < KC; ++kc) *reinterpret_cast<dtp_u32x4*>(&tile[16 * mt + j][d0 + 32 * kc + 8 * g]) = cur[mt][kc];
+            for (int kc = 0; kc < KC; ++kc) *reinterpret_cast<u32x4_t*>(&tile[16 * mt + j][d0 + 32 * kc + 8 * g]) = cur[mt][kc];
         {
             const int pr = tid / (R / 8), pc = tid % (R / 8);
-            if (pr < DTB_TM) *reinterpret_cast<dtp_u32x4*>(&xt[pr][8 * pc]) = xcur;
+            if (pr < DTB_TM) *reinterpret_cast<u32x4_t*>(&xt[pr][8 * pc]) = xcur;
         }
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
@@ -312,32 +281,29 @@ __global__ __launch_bounds__(64 * DTB_WAVES) void dtproj_bwd_kernel(const mix_ar
 #pragma unroll
             for (int w = 0; w < DTB_WAVES; ++w) s += *reinterpret_cast<const f32x4*>(&osum[w][q][l][0]);
             const int mt = q / NR, nr = q % NR;
-            const u32x2_t pk = {dtp_mfma<T>::pack(s[0], s[1]), dtp_mfma<T>::pack(s[2], s[3])};
+            const u32x2_t pk = {mfma<T>::pack(s[0], s[1]), mfma<T>::pack(s[2], s[3])};
             const int orow = t * DTB_TM + 16 * mt + (l & 15);
             if (orow < p.rows) *reinterpret_cast<u32x2_t*>(O + (int64_t)orow * p.dxd_sr + 16 * nr + 4 * (l >> 4)) = pk;
         }
         // ---- product 2: dW^T[r][d] += xdt^T[r][m] * dd[m][d], K = the tile's 32 rows; both operands through transposing LDS reads:
         //      lane (j, g) supplies the 8-byte piece (row 8 g + (j >> 2) [+ 4], columns c0 + 4 (j & 3) ..) and receives rows 8 g .. 8 g + 7 of column c0 + j
-        dtp_u32x4 xa[NR];
+        u32x4_t xa[NR];
 #pragma unroll
         for (int nr = 0; nr < NR; ++nr) {
             const tr_v4s a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr)&xt[8 * g + (j >> 2)][16 * nr + 4 * (j & 3)]);
             const tr_v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr)&xt[8 * g + 4 + (j >> 2)][16 * nr + 4 * (j & 3)]);
             const u32x2_t w0 = __builtin_bit_cast(u32x2_t, a0), w1 = __builtin_bit_cast(u32x2_t, a1);
-            xa[nr] = (dtp_u32x4){w0.x, w0.y, w1.x, w1.y};
+            xa[nr] = (u32x4_t){w0.x, w0.y, w1.x, w1.y};
         }
 #pragma unroll
         for (int nt = 0; nt < 2 * KC; ++nt) {
             const tr_v4s b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr)&tile[8 * g + (j >> 2)][d0 + 16 * nt + 4 * (j & 3)]);
             const tr_v4s b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr)&tile[8 * g + 4 + (j >> 2)][d0 + 16 * nt + 4 * (j & 3)]);
             const u32x2_t w0 = __builtin_bit_cast(u32x2_t, b0), w1 = __builtin_bit_cast(u32x2_t, b1);
-            const dtp_u32x4 bf = {w0.x, w0.y, w1.x, w1.y};
+            const u32x4_t bf = {w0.x, w0.y, w1.x, w1.y};
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
-                if constexpr (std::is_same<T, bf16_t>::value)
-                    accw[nr][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dtp_bf16x8, xa[nr]), __builtin_bit_cast(dtp_bf16x8, bf), accw[nr][nt], 0, 0, 0);
-                else
-                    accw[nr][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dtp_f16x8, xa[nr]), __builtin_bit_cast(dtp_f16x8, bf), accw[nr][nt], 0, 0, 0);
+                accw[nr][nt] = mfma<T>::m16(xa[nr], bf, accw[nr][nt]);
             }
         }
         __syncthreads();                                           // the images are rewritten by the next tile
@@ -393,9 +359,7 @@ static bool pairs_dtproj_bwd(const dm_dtproj_bwd_args& x, const dm_dtproj_bwd_ar
 static int run_dtproj_bwd(const dm_dtproj_bwd_args& a, const dm_dtproj_bwd_args* second, hipStream_t st) {
     const int rc = (a.io_dtype == DM_BF16) ? dtproj_bwd_launch<bf16_t>(a, second, st) : dtproj_bwd_launch<f16_t>(a, second, st);
     if (rc != DM_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_dtproj_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_dtproj_bwd");
 }
 
 }  // namespace dm

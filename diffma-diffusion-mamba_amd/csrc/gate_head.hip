@@ -15,31 +15,7 @@ namespace dm {
 
 constexpr int GH_WAVES = 4;
 
-template <typename T, int VEC>
-__device__ __forceinline__ void gh_ld(float (&dst)[VEC], const T* p) {
-    alignas(16) T tmp[VEC];
-    if constexpr (VEC * sizeof(T) == 16) *(f32x4*)tmp = *(const f32x4*)p;
-    else if constexpr (VEC * sizeof(T) == 8) *(f32x2*)tmp = *(const f32x2*)p;
-    else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) tmp[j] = p[j];
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) dst[j] = io<T>::ld(&tmp[j]);
-}
-template <typename T, int VEC>
-__device__ __forceinline__ void gh_st(T* p, const float (&src)[VEC]) {
-    alignas(16) T tmp[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) io<T>::st(&tmp[j], src[j]);
-    if constexpr (VEC * sizeof(T) == 16) *(f32x4*)p = *(const f32x4*)tmp;
-    else if constexpr (VEC * sizeof(T) == 8) *(f32x2*)p = *(const f32x2*)tmp;
-    else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) p[j] = tmp[j];
-    }
-}
-
+// not sigmoid_f (v_rcp_f32 of 1 + v_exp_f32): a true division on __expf, which rounds differently
 __device__ __forceinline__ float gh_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 template <typename T, int VEC, int NIT>
@@ -52,8 +28,8 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gate_head_fwd_kernel(const dm_g
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { b1[it][j] = 0.f; w2[it][j] = 0.f; }
         if (c < p.C) {
-            if (p.b1) gh_ld<float, VEC>(b1[it], p.b1 + c);
-            gh_ld<float, VEC>(w2[it], p.w2 + c);
+            if (p.b1) ld_vec<float, VEC>(b1[it], p.b1 + c);
+            ld_vec<float, VEC>(w2[it], p.w2 + c);
         }
     }
     const float b2 = p.b2 ? p.b2[0] : 0.f;
@@ -65,7 +41,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gate_head_fwd_kernel(const dm_g
             const int c = (it * 64 + lane) * VEC;
             if (c < p.C) {
                 float h[VEC];
-                gh_ld<T, VEC>(h, (const T*)p.h + r * p.h_sr + c);
+                ld_vec<T, VEC>(h, (const T*)p.h + r * p.h_sr + c);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     const float x = h[j] + b1[it][j];
@@ -90,8 +66,8 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gate_head_bwd_kernel(const dm_g
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { b1[it][j] = 0.f; w2[it][j] = 0.f; acc1[it][j] = 0.f; acc2[it][j] = 0.f; }
         if (c < p.C) {
-            if (p.b1) gh_ld<float, VEC>(b1[it], p.b1 + c);
-            gh_ld<float, VEC>(w2[it], p.w2 + c);
+            if (p.b1) ld_vec<float, VEC>(b1[it], p.b1 + c);
+            ld_vec<float, VEC>(w2[it], p.w2 + c);
         }
     }
     float accb = 0.f;
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gate_head_bwd_kernel(const dm_g
             const int c = (it * 64 + lane) * VEC;
             if (c < p.C) {
                 float h[VEC], dh[VEC];
-                gh_ld<T, VEC>(h, (const T*)p.h + r * p.h_sr + c);
+                ld_vec<T, VEC>(h, (const T*)p.h + r * p.h_sr + c);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     const float x = h[j] + b1[it][j];
@@ -115,7 +91,7 @@ __global__ __launch_bounds__(64 * GH_WAVES) void gate_head_bwd_kernel(const dm_g
                     acc1[it][j] += g;
                     acc2[it][j] += dpre * x * sg;
                 }
-                gh_st<T, VEC>((T*)p.dh + r * p.dh_sr + c, dh);
+                st_vec<T, VEC>((T*)p.dh + r * p.dh_sr + c, dh);
             }
         }
     }
@@ -188,9 +164,7 @@ static int gate_head_entry(const dm_gate_head_args* args, void* stream, bool bwd
         default: set_error("%s: unsupported dtype %d", who, a.io_dtype); return DM_ERR_DTYPE;
     }
     if (rc != DM_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status(who);
 }
 
 }  // namespace dm

@@ -23,7 +23,7 @@
 // one output row, and leaves as one 8-byte (16-bit C) or 16-byte (fp32 C) store.
 // Workgroup = 4 waves (2 x 2) on a BM x BN tile, BK = 32; the next tile's global loads are in flight (registers) while the
 // current one is multiplied.
-#include "dm_common.h"
+#include "dm_mfma.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -50,36 +50,12 @@ typedef short gm_v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) gm_v4s* gm_tr_ptr;
 typedef uint32_t gm_u32x2 __attribute__((ext_vector_type(2)));
 
-typedef __bf16 gm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gm_f16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t gm_u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct gm_mfma;
-template <> struct gm_mfma<bf16_t> {
-    static __device__ __forceinline__ f32x4 run(const gm_u32x4& a, const gm_u32x4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gm_bf16x8, a), __builtin_bit_cast(gm_bf16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) { return dm_cvt_pk_bf16(lo, hi); }
-};
-template <> struct gm_mfma<f16_t> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ f32x4 run(const gm_u32x4& a, const gm_u32x4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gm_f16x8, a), __builtin_bit_cast(gm_f16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        h2 v;
-        v.x = (_Float16)lo;
-        v.y = (_Float16)hi;
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
-
 // One operand tile: ROWS rows x BK k.  KMAJOR: 16-byte pieces along k (ROWS * BK / 8 pieces); row-major source: 16-byte pieces along
 // the row index at one k (BK * ROWS / 8 pieces).  256 threads -> ROWS * BK / 2048 pieces per thread either way.
 template <typename T, int ROWS, int BK, bool KMAJOR>
 struct gm_tile {
     static constexpr int NP = ROWS * BK / 2048, KP = BK / 8;
-    gm_u32x4 v[NP];
+    u32x4_t v[NP];
     static __device__ __forceinline__ void where(int q, int& row, int& k) {
         if (KMAJOR) { row = q / KP; k = (q % KP) * 8; }                              // KP pieces of 8 k per row
         else { k = (q >> 2) & (BK - 1); row = ((q / (4 * BK)) * 4 + (q & 3)) * 8; }  // 4 neighbouring lanes read 64 contiguous bytes of one k
@@ -92,8 +68,8 @@ struct gm_tile {
             where(tid + p * 256, row, k);
             const bool ok = (r0 + row < nrows) && (k0 + k < Kc);          // (sizes are multiples of 8 along the contiguous index)
             const int64_t off = KMAJOR ? (int64_t)(r0 + row) * ld + (k0 + k) : (int64_t)(k0 + k) * ld + (r0 + row);
-            const gm_u32x4 z = {0u, 0u, 0u, 0u};
-            v[p] = ok ? *reinterpret_cast<const gm_u32x4*>(base + off) : z;
+            const u32x4_t z = {0u, 0u, 0u, 0u};
+            v[p] = ok ? *reinterpret_cast<const u32x4_t*>(base + off) : z;
         }
     }
     __device__ __forceinline__ void store(uint16_t* lds, int tid) const {
@@ -101,23 +77,23 @@ struct gm_tile {
         for (int p = 0; p < NP; ++p) {
             int row, k;
             where(tid + p * 256, row, k);
-            if (KMAJOR) *reinterpret_cast<gm_u32x4*>(lds + gm_lds<BK>::off(row, k)) = v[p];
-            else *reinterpret_cast<gm_u32x4*>(lds + k * gm_rm<ROWS>::LROW + row) = v[p];          // as loaded: [k][row .. row + 7]
+            if (KMAJOR) *reinterpret_cast<u32x4_t*>(lds + gm_lds<BK>::off(row, k)) = v[p];
+            else *reinterpret_cast<u32x4_t*>(lds + k * gm_rm<ROWS>::LROW + row) = v[p];          // as loaded: [k][row .. row + 7]
         }
     }
 };
 
 // fragment of operand rows r0 + (l & 15), contraction kk + 8 (l >> 4) .. + 7, from either LDS image
 template <int ROWS, int BK, bool KMAJOR>
-__device__ __forceinline__ gm_u32x4 gm_frag(const uint16_t* lds, int r0, int kk, int fi, int fg) {
+__device__ __forceinline__ u32x4_t gm_frag(const uint16_t* lds, int r0, int kk, int fi, int fg) {
     if constexpr (KMAJOR) {
-        return *reinterpret_cast<const gm_u32x4*>(lds + gm_lds<BK>::off(r0 + fi, kk + 8 * fg));
+        return *reinterpret_cast<const u32x4_t*>(lds + gm_lds<BK>::off(r0 + fi, kk + 8 * fg));
     } else {
         const uint16_t* q = lds + (kk + 8 * fg + (fi >> 2)) * gm_rm<ROWS>::LROW + r0 + 4 * (fi & 3);
         const gm_v4s a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_tr_ptr)q);
         const gm_v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((gm_tr_ptr)(q + 4 * gm_rm<ROWS>::LROW));
         const gm_u32x2 w0 = __builtin_bit_cast(gm_u32x2, a0), w1 = __builtin_bit_cast(gm_u32x2, a1);
-        return (gm_u32x4){w0.x, w0.y, w1.x, w1.y};
+        return (u32x4_t){w0.x, w0.y, w1.x, w1.y};
     }
 }
 
@@ -157,7 +133,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const mix_args<dm_gemm_args> 
         }
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 32) {
-            gm_u32x4 fa[TM], fb[TN];
+            u32x4_t fa[TM], fb[TN];
 #pragma unroll
             for (int j = 0; j < TM; ++j) fa[j] = gm_frag<BM, BK, AK>(As, wm + 16 * j, kk, fi, fg);
 #pragma unroll
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const mix_args<dm_gemm_args> 
 #pragma unroll
             for (int i = 0; i < TN; ++i)
 #pragma unroll
-                for (int j = 0; j < TM; ++j) acc[i][j] = gm_mfma<T>::run(fb[i], fa[j], acc[i][j]);      // rows = n, columns = m
+                for (int j = 0; j < TM; ++j) acc[i][j] = mfma<T>::m16(fb[i], fa[j], acc[i][j]);      // rows = n, columns = m
         }
     }
     // lane l holds C[m = .. + (l & 15)][n = .. + 4 (l >> 4) + r], r = 0..3
@@ -192,7 +168,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const mix_args<dm_gemm_args> 
                 if constexpr (std::is_same<TC, float>::value) {
                     *reinterpret_cast<f32x4*>(dst) = v;
                 } else {
-                    const u32x2 w = {gm_mfma<T>::pack(v.x, v.y), gm_mfma<T>::pack(v.z, v.w)};
+                    const u32x2 w = {mfma<T>::pack(v.x, v.y), mfma<T>::pack(v.z, v.w)};
                     *reinterpret_cast<u32x2*>(dst) = w;
                 }
             }
@@ -249,9 +225,7 @@ static int run_gemm(const dm_gemm_args& a, const dm_gemm_args* second, hipStream
     const bool c32 = a.c_dtype == DM_F32;
     if (a.ab_dtype == DM_BF16) { if (c32) gemm_launch_t<bf16_t, float>(a, second, st); else gemm_launch_t<bf16_t, bf16_t>(a, second, st); }
     else { if (c32) gemm_launch_t<f16_t, float>(a, second, st); else gemm_launch_t<f16_t, f16_t>(a, second, st); }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gemm: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gemm");
 }
 
 }  // namespace dm

@@ -21,7 +21,7 @@
 // instruction: row l >> 2, 16-byte slot l & 3 of a 16-row group) -- the swizzle is therefore applied to the SOURCE address: slot s of
 // row r holds the row's piece s ^ ((r >> 2) & 3).  A fragment read (ds_read_b128: lane = row, all lanes one piece) then touches
 // 16 distinct 16-byte slots of the 256-byte bank window per 16-lane group: conflict-free.
-#include "dm_common.h"
+#include "dm_mfma.h"
 #include <cstdlib>
 
 namespace dm {
@@ -41,30 +41,7 @@ struct gl_args {
     int MB, NT, T, TX;           // row blocks, column tiles, tiles, tiles per XCD
 };
 
-typedef __bf16 gl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gl_f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* gl_lds_ptr;
-
-template <typename T> struct gl_mfma;
-template <> struct gl_mfma<bf16_t> {
-    static __device__ __forceinline__ f32x16 run(const u32x4_t& a, const u32x4_t& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gl_bf16x8, a), __builtin_bit_cast(gl_bf16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) { return dm_cvt_pk_bf16(lo, hi); }
-};
-template <> struct gl_mfma<f16_t> {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ f32x16 run(const u32x4_t& a, const u32x4_t& b, const f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gl_f16x8, a), __builtin_bit_cast(gl_f16x8, b), c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint32_t pack(float lo, float hi) {
-        h2 v;
-        v.x = (_Float16)lo;
-        v.y = (_Float16)hi;
-        return __builtin_bit_cast(uint32_t, v);
-    }
-};
 
 __device__ __forceinline__ void gl_swap32(uint32_t& a, uint32_t& b) {        // a[lanes 32..63] <-> b[lanes 0..31]
     auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
@@ -193,8 +170,8 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
                     uint32_t w[8];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        w[2 * q] = gl_mfma<T>::pack(v[4 * q], v[4 * q + 1]);
-                        w[2 * q + 1] = gl_mfma<T>::pack(v[4 * q + 2], v[4 * q + 3]);
+                        w[2 * q] = mfma<T>::pack(v[4 * q], v[4 * q + 1]);
+                        w[2 * q + 1] = mfma<T>::pack(v[4 * q + 2], v[4 * q + 3]);
                     }
                     // quads of lanes l and l + 32 are neighbours in the row: after the swaps a lane below 32 holds columns 0..7 and
                     // 16..23 of the 32-column block, its partner 8..15 and 24..31
@@ -249,8 +226,8 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
         FXN[1] = read_x(NSTAGE, NHALF, 1);                                                                                   \
         __builtin_amdgcn_s_setprio(1);                                                            \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                      \
-            acc[i][0] = gl_mfma<T>::run(fw[i], FXC[0], acc[i][0]);                                                           \
-            acc[i][1] = gl_mfma<T>::run(fw[i], FXC[1], acc[i][1]);                                                           \
+            acc[i][0] = mfma<T>::m32(fw[i], FXC[0], acc[i][0]);                                                              \
+            acc[i][1] = mfma<T>::m32(fw[i], FXC[1], acc[i][1]);                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
             fw[i] = read_w(NSTAGE, NHALF, i);                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
@@ -354,7 +331,5 @@ extern "C" int dm_gemm_large(const dm_gemm_args* args, void* stream) {
         const int rc = dm_gemm(&t, stream);
         if (rc != DM_OK) return rc;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gemm_large: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gemm_large");
 }

@@ -105,9 +105,7 @@ static int launch_merge(const dm_merge_args& a, const dm_merge_args* second, hip
         if (a.gate) hipLaunchKernelGGL((merge_kernel<TI, TO, 1, true>), grid, dim3(256), 0, st, m);
         else hipLaunchKernelGGL((merge_kernel<TI, TO, 1>), grid, dim3(256), 0, st, m);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_token_merge: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_token_merge");
 }
 
 static int check_merge(const dm_merge_args& a) {
@@ -187,9 +185,7 @@ static int launch_gate_bwd(const dm_gate_bwd_args& a, const dm_gate_bwd_args* se
         dim3 grid((a.dim + 255) / 256, a.seqlen, a.batch * gz);
         hipLaunchKernelGGL((gate_bwd_kernel<T, 1>), grid, dim3(256), 0, st, m);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_gate_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_gate_bwd");
 }
 
 static int check_gate_bwd(const dm_gate_bwd_args& a) {
@@ -274,9 +270,7 @@ static int run_colsum(const dm_colsum_args& a, const dm_colsum_args* second, hip
     const mix_args<dm_colsum_args> m = mix_make(a, second, gz);
     dim3 grid((unsigned)((a.cols / 4 + WAVE - 1) / WAVE), 1, gz);
     hipLaunchKernelGGL(colsum_kernel, grid, dim3(64 * CS_WAVES), 0, st, m);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_colsum_f32: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_colsum_f32");
 }
 }  // namespace dm
 
@@ -332,9 +326,7 @@ static int run_sum_partials(const dm_sum_partials_args& a, const dm_sum_partials
         case DM_F16: hipLaunchKernelGGL((sum_partials_kernel<f16_t>), grid, dim3(256), 0, st, m); break;
         default: set_error("dm_sum_partials: bad out_dtype %d", a.out_dtype); return DM_ERR_DTYPE;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_sum_partials: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_sum_partials");
 }
 }  // namespace dm
 

@@ -138,9 +138,7 @@ extern "C" int dm_grads_nonfinite(const dm_adamw_args* args, void* stream) {
     if (!a.tensors || !a.block_tensor || !a.block_chunk || !a.nonfinite_out) { set_error("dm_grads_nonfinite: null table / output pointer"); return DM_ERR_ARG; }
     if (a.ntensors <= 0 || a.nblocks <= 0) { set_error("dm_grads_nonfinite: non-positive ntensors / nblocks"); return DM_ERR_ARG; }
     hipLaunchKernelGGL(grads_nonfinite_kernel, dim3(a.nblocks), dim3(AW_THREADS), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_grads_nonfinite: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_grads_nonfinite");
 }
 
 extern "C" int dm_adamw_chunk(void) { return dm::AW_CHUNK; }
@@ -157,7 +155,5 @@ extern "C" int dm_adamw_ema_step(const dm_adamw_args* args, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(adamw_steps_kernel, dim3((a.ntensors + 63) / 64), dim3(64), 0, st, a);
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(a.nblocks), dim3(AW_THREADS), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_adamw_ema_step: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_adamw_ema_step");
 }

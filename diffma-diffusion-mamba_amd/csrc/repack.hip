@@ -143,9 +143,7 @@ static int launch_repack(const dm_repack_args& a, hipStream_t st) {
         else if (vl == V8) launch_repack_dir<E, V8, 1>(a, grid, st);
         else launch_repack_dir<E, 1, 1>(a, grid, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_repack: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_repack");
 }
 
 }  // namespace dm

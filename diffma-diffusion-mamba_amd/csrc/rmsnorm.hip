@@ -12,32 +12,6 @@ namespace dm {
 constexpr int RMS_WAVES = 4;
 constexpr int RMS_ROWS_PER_BLOCK = 16;     // backward: rows per workgroup = rows per weight-gradient partial row (4 per wave)
 
-__device__ __forceinline__ float rms_wave_sum(float v) { return wave_sum_dpp(v); }
-
-template <typename T>
-__device__ __forceinline__ void rms_ld4(float (&dst)[4], const T* p) {
-    if constexpr (sizeof(T) == 4) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
-        dst[0] = q.x; dst[1] = q.y; dst[2] = q.z; dst[3] = q.w;
-    } else {
-        alignas(8) T tmp[4];
-        *reinterpret_cast<f32x2*>(tmp) = *reinterpret_cast<const f32x2*>(p);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dst[j] = io<T>::ld(&tmp[j]);
-    }
-}
-template <typename T>
-__device__ __forceinline__ void rms_st4(T* p, const float (&src)[4]) {
-    if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<f32x4*>(p) = (f32x4){src[0], src[1], src[2], src[3]};
-    } else {
-        alignas(8) T tmp[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) io<T>::st(&tmp[j], src[j]);
-        *reinterpret_cast<f32x2*>(p) = *reinterpret_cast<const f32x2*>(tmp);
-    }
-}
-
 template <typename T, int NIT>
 __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_fwd_kernel(const dm_rmsnorm_merge_args p) {
     const int lane = threadIdx.x & 63;
@@ -58,7 +32,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_fwd_kernel(const
         for (int it = 0; it < NIT; ++it) {
             const int c = (it * 64 + lane) * 4;
             if (c < C) {
-                rms_ld4<T>(v[it], yr + c);
+                ld_vec<T, 4>(v[it], yr + c);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[it][j] = 0.f;
@@ -66,7 +40,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_fwd_kernel(const
 #pragma unroll
             for (int j = 0; j < 4; ++j) q += v[it][j] * v[it][j];
         }
-        const float rstd = rsqrtf(rms_wave_sum(q) / (float)C + p.eps);
+        const float rstd = rsqrtf(wave_sum_dpp(q) / (float)C + p.eps);
         if (lane == 0) p.rstd[(int64_t)k * p.rows + r] = rstd;
 #pragma unroll
         for (int it = 0; it < NIT; ++it)
@@ -79,10 +53,10 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_fwd_kernel(const
         const int c = (it * 64 + lane) * 4;
         if (c < C) {
             float w[4], o[4];
-            rms_ld4<float>(w, p.weight + c);
+            ld_vec<float, 4>(w, p.weight + c);
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = acc[it][j] * w[j];
-            rms_st4<T>(orow + c, o);
+            st_vec<T, 4>(orow + c, o);
         }
     }
 }
@@ -99,7 +73,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
     for (int it = 0; it < NIT; ++it) {
         const int c = (it * 64 + lane) * 4;
         if (c < C) {
-            rms_ld4<float>(w[it], p.weight + c);
+            ld_vec<float, 4>(w[it], p.weight + c);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) w[it][j] = 0.f;
@@ -117,7 +91,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
         for (int it = 0; it < NIT; ++it) {
             const int c = (it * 64 + lane) * 4;
             if (c < C) {
-                rms_ld4<T>(g[it], gr + c);
+                ld_vec<T, 4>(g[it], gr + c);
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) g[it][j] = 0.f;
@@ -129,7 +103,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
             for (int it = 0; it < NIT; ++it) {
                 const int c = (it * 64 + lane) * 4;
                 if (c < C) {
-                    rms_ld4<T>(v[it], yr + c);
+                    ld_vec<T, 4>(v[it], yr + c);
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[it][j] = 0.f;
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
                     dot += g[it][j] * w[it][j] * v[it][j];
                 }
             if (k + 1 < p.nslab) load_slab(k + 1, vn);       // the next slab's row is in flight under this one's reduction
-            const float coef = rms_wave_sum(dot) * rstd * rstd * rstd / (float)C;
+            const float coef = wave_sum_dpp(dot) * rstd * rstd * rstd / (float)C;
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int c = (it * 64 + lane) * 4;
@@ -161,7 +135,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
                     o[j] = rstd * g[it][j] * w[it][j] - v[it][j] * coef;
                     dwl[it][j] += g[it][j] * v[it][j] * rstd;
                 }
-                if (c < C) rms_st4<T>(dyr + c, o);
+                if (c < C) st_vec<T, 4>(dyr + c, o);
             }
         }
     }
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(64 * RMS_WAVES) void rmsnorm_merge_bwd_kernel(const
 #pragma unroll
                     for (int wv = 0; wv < RMS_WAVES; ++wv) o[j] += part_lds[wv][it * 4 + j][lane];
                 }
-                rms_st4<float>(p.dw_part + (int64_t)blockIdx.x * C + c, o);
+                st_vec<float, 4>(p.dw_part + (int64_t)blockIdx.x * C + c, o);
             }
         }
     }
@@ -206,9 +180,7 @@ static int rms_launch(const dm_rmsnorm_merge_args& a, hipStream_t st, bool bwd) 
     else if (nit <= 8) rms_launch2<T, 8>(a, st, bwd);
     else if (nit <= 12) rms_launch2<T, 12>(a, st, bwd);
     else rms_launch2<T, 16>(a, st, bwd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_rmsnorm_merge: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_rmsnorm_merge");
 }
 
 static int rms_entry(const dm_rmsnorm_merge_args* args, void* stream, bool bwd) {

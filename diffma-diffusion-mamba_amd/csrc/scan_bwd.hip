@@ -1,7 +1,6 @@
 // C entry point of scan_bwd: validation + dtype dispatch (kernels live in scan_bwd_impl.h / scan_bwd_<dtype>.hip)
 #include "dm_common.h"
 namespace dm {
-constexpr int BWD_SUB = 4;     // = checkpoint spacing (scan_bwd_impl.h)
 int scan_bwd_f32(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
 int scan_bwd_bf16(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
 int scan_bwd_f16(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st);
@@ -14,7 +13,7 @@ static int check_scan_bwd(const dm_scan_bwd_args& a) {
     if ((a.z != nullptr) != (a.dz != nullptr)) { set_error("dm_selective_scan_bwd: dz must be given iff z is"); return DM_ERR_ARG; }
     if (a.nseq <= 0 || a.dim <= 0 || a.seqlen <= 0 || a.ngroups <= 0) { set_error("dm_selective_scan_bwd: non-positive size"); return DM_ERR_ARG; }
     if (a.nseq > 65535) { set_error("dm_selective_scan_bwd: nseq %d > 65535", a.nseq); return DM_ERR_ARG; }
-    if (a.ckpt_every != BWD_SUB) { set_error("dm_selective_scan_bwd: ckpt_every must be %d", BWD_SUB); return DM_ERR_ARG; }
+    if (a.ckpt_every != DM_SCAN_CKPT_EVERY) { set_error("dm_selective_scan_bwd: ckpt_every must be %d", DM_SCAN_CKPT_EVERY); return DM_ERR_ARG; }
     if (!a.ckpt) { set_error("dm_selective_scan_bwd: ckpt (the checkpoints written by dm_selective_scan_fwd) is required"); return DM_ERR_ARG; }
     if (a.ckpt && a.ckpt_dtype != (a.io_dtype == DM_BF16 ? DM_BF16 : DM_F32)) {
         set_error("dm_selective_scan_bwd: ckpt_dtype must be DM_BF16 for bf16 I/O and DM_F32 otherwise"); return DM_ERR_DTYPE;

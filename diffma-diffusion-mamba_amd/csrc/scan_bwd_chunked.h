@@ -36,7 +36,7 @@ __device__ __forceinline__ float row_sum16(float x) {
 template <typename T, typename TBC, bool HAS_Z, bool IDX, int DMODE, int NW, int LC, bool ASH = false>   // DMODE: scan_bwd_impl.h
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void scan_bwd_chunked_kernel(const mix_args<dm_scan_bwd_args> pm) {
     const dm_scan_bwd_args& p = pm.a[blockIdx.z];      // grid.z = congruent launches sharing this one (the two mixers of a block)
-    constexpr int N = 16, NPL = N / 2, SUB = BWD_SUB, M = 2 * N;
+    constexpr int N = 16, NPL = N / 2, SUB = DM_SCAN_CKPT_EVERY, M = 2 * N;
     constexpr int ES = (int)sizeof(T);
     constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value;
     static_assert(LC % SUB == 0, "chunks must start on checkpoints");
@@ -432,9 +432,7 @@ static int launch_bwd_chunked(const dm_scan_bwd_args& a, const dm_scan_bwd_args*
         else DM_BWDC(false, false);
     }
 #undef DM_BWDC
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_selective_scan_bwd (chunked): launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_selective_scan_bwd (chunked)");
 }
 
 template <typename T>

@@ -38,7 +38,7 @@
 namespace dm {
 
 constexpr int BWD_CK = 8;      // steps per staging chunk (B/C rows and dB/dC partials go through LDS once per chunk)
-constexpr int BWD_SUB = 4;     // checkpoint spacing = steps whose recomputed states are held in registers at once
+// (sub-chunk length SUB = DM_SCAN_CKPT_EVERY, the checkpoint spacing: the steps whose recomputed states are held in registers at once)
 constexpr int BWD_WAVES = 4;   // waves per workgroup
 
 // ---- cross-lane helpers ----------------------------------------------------------------------
@@ -143,7 +143,7 @@ __device__ __forceinline__ void lds_ld_vec(float (&v)[NS], lds_cfptr row) {
 // direction twice); the returned ddelta is the gradient of the RAW value in every mode: softplus'(x) = 1 - exp(-softplus(x)).
 template <typename T, typename TBC, int N, int SPLIT, bool HAS_Z, bool IDX, int DMODE, bool ASH = false>
 __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(N <= 16 ? 2 : 1))) void scan_bwd_kernel(const dm_scan_bwd_args p) {
-    constexpr int NS = N / SPLIT, NPL = NS / 2, CW = WAVE / SPLIT, CK = BWD_CK, SUB = BWD_SUB, M = 2 * NS, R = M / 4;
+    constexpr int NS = N / SPLIT, NPL = NS / 2, CW = WAVE / SPLIT, CK = BWD_CK, SUB = DM_SCAN_CKPT_EVERY, M = 2 * NS, R = M / 4;
     constexpr int ES = (int)sizeof(T);
     constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value && M % 16 == 0;   // dB/dC lane-group sums on the matrix pipe
     // HALVES: the lane's 16 states as two groups of 8 walked one after the other, the recomputed steps' decay factors reused by the sweep
@@ -666,9 +666,7 @@ static int launch_bwd(const dm_scan_bwd_args& a, hipStream_t st) {
         if (idx) launch_bwd2<T, TBC, N, false, true>(a, st, grid);
         else launch_bwd2<T, TBC, N, false, false>(a, st, grid);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_selective_scan_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_selective_scan_bwd");
 }
 
 template <typename T, typename TBC>

@@ -1,7 +1,6 @@
 // C entry point of scan_fwd: validation + dtype dispatch (kernels live in scan_fwd_impl.h / scan_fwd_<dtype>.hip)
 #include "dm_common.h"
 namespace dm {
-constexpr int FWD_CKE = 4;      // checkpoint spacing (scan_fwd_impl.h)
 int scan_fwd_f32(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
 int scan_fwd_bf16(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
 int scan_fwd_f16(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st);
@@ -34,8 +33,8 @@ static int check_scan_fwd(const dm_scan_fwd_args& a) {
     if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) {
         set_error("dm_selective_scan_fwd: nseq %% batch_per_dir != 0"); return DM_ERR_ARG;
     }
-    if (a.ckpt && a.ckpt_every != FWD_CKE) {
-        set_error("dm_selective_scan_fwd: ckpt_every must be %d", FWD_CKE); return DM_ERR_ARG;
+    if (a.ckpt && a.ckpt_every != DM_SCAN_CKPT_EVERY) {
+        set_error("dm_selective_scan_fwd: ckpt_every must be %d", DM_SCAN_CKPT_EVERY); return DM_ERR_ARG;
     }
     if (a.ckpt && a.ckpt_dtype != (a.io_dtype == DM_BF16 ? DM_BF16 : DM_F32)) {
         set_error("dm_selective_scan_fwd: ckpt_dtype must be DM_BF16 for bf16 I/O and DM_F32 otherwise"); return DM_ERR_DTYPE;

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64 * NW) void scan_fwd_chunked_kernel(const mix_arg
     const TBC* __restrict__ Cg = (const TBC*)p.C + (int64_t)s * p.C_ss + (int64_t)grp * p.C_sg;
     constexpr bool CK_PACKED = std::is_same<T, bf16_t>::value;
     constexpr int CK_ROWS = CK_PACKED ? NP : N;
-    const int nck = (L + FWD_CKE - 1) / FWD_CKE;
+    const int nck = (L + DM_SCAN_CKPT_EVERY - 1) / DM_SCAN_CKPT_EVERY;
     const rsrc_t r_ck = make_rsrc(CKPT ? (const uint32_t*)p.ckpt + (int64_t)s * nck * CK_ROWS * p.dim : nullptr);
 
     // ---- this chunk's inputs: requested up front, kept in registers for both passes ------------------------------
@@ -147,8 +147,8 @@ __global__ __launch_bounds__(64 * NW) void scan_fwd_chunked_kernel(const mix_arg
             }
             const float y = scan_step<N, HAS_Z, false, ASH>(h, A2, Bc, Cc, uu[j], dl[j], zz[j], Dv, 0.0f);
             bio<T>::st(r_o, vo, (IDX ? oidx[l] : l) * sl_o, y);
-            if (CKPT && ((l + 1) % FWD_CKE == 0 || l + 1 == L)) {       // training: the state entering every 4-step chunk (wave-uniform);
-                const int ci = (l + 1 < L) ? (l + 1) / FWD_CKE : 0;      // slot 0 = the state after the last step
+            if (CKPT && ((l + 1) % DM_SCAN_CKPT_EVERY == 0 || l + 1 == L)) {       // training: the state entering every 4-step chunk (wave-uniform);
+                const int ci = (l + 1 < L) ? (l + 1) / DM_SCAN_CKPT_EVERY : 0;      // slot 0 = the state after the last step
                 if constexpr (CK_PACKED) {                               // [chunk][N/8][d][4 words], see scan_fwd_impl.h
                     uint32_t w[NP];
 #pragma unroll
@@ -223,9 +223,7 @@ static int launch_fwd_chunked(const dm_scan_fwd_args& a, const dm_scan_fwd_args*
         if (idx) launch_fwd_chunked2<T, TBC, false, true>(a, second, st);
         else launch_fwd_chunked2<T, TBC, false, false>(a, second, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_selective_scan_fwd (chunked): launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_selective_scan_fwd (chunked)");
 }
 
 template <typename T>

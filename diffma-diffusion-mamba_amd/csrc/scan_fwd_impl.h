@@ -26,7 +26,6 @@
 
 namespace dm {
 
-constexpr int FWD_CKE = 4;     // steps between checkpoints (the backward's sub-chunk length)
 #ifndef DM_FWD_F32_WAVES
 #define DM_FWD_F32_WAVES 1     // minimum waves per SIMD requested for the fp32-I/O instantiations (register budget 512 / waves)
 #endif
@@ -66,7 +65,7 @@ __device__ __forceinline__ float scan_step(f32x2 (&h)[N / 2], const f32x2 (&A2)[
 }
 
 // IDX : z_row_index / out_row_index tables are used (both non-null)
-// CKPT: the state is written to p.ckpt after every FWD_CKE = 4 steps (fp32, or bf16 pairs for bf16 I/O)
+// CKPT: the state is written to p.ckpt after every DM_SCAN_CKPT_EVERY = 4 steps (fp32, or bf16 pairs for bf16 I/O)
 // ACC : DM_FLAG_OUT_ACCUMULATE -- the launch ADDS its outputs to what `out` already holds (read-add-store through
 //       out_row_index) instead of storing them.  The host walks the directions of the CrossMerge with one launch each into ONE
 //       token-order buffer (direction 0 stores, the others accumulate): the merge sum happens here and the separate
@@ -135,7 +134,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
 
     constexpr bool CK_PACKED = std::is_same<T, bf16_t>::value;      // checkpoint = pairs of bf16 in one 32-bit word
     constexpr int CK_ROWS = CK_PACKED ? NP : N;                     // 32-bit rows of [dim] per checkpoint
-    const int nchunk = CKPT ? (L + FWD_CKE - 1) / FWD_CKE : 0;
+    const int nchunk = CKPT ? (L + DM_SCAN_CKPT_EVERY - 1) / DM_SCAN_CKPT_EVERY : 0;
     const rsrc_t r_ck = make_rsrc(CKPT ? (const uint32_t*)p.ckpt + (int64_t)s * nchunk * CK_ROWS * p.dim : nullptr);
     auto store_slot = [&](int c) {
         if constexpr (CK_PACKED) {          // [chunk][N/8][d][4 words]: two dense 16-byte stores per lane (8 dword stores until round 3)
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
         }
     };
     auto store_ckpt = [&](int done) {                               // done = steps finished (wave-uniform)
-        if (done < L) store_slot(done / FWD_CKE);                   // state entering chunk done / FWD_CKE
+        if (done < L) store_slot(done / DM_SCAN_CKPT_EVERY);                   // state entering chunk done / DM_SCAN_CKPT_EVERY
     };
 
     // ---- register prefetch ring: rows of block b+1 are requested before block b is computed ----
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
             float y = scan_step<N, HAS_Z, SOFTPLUS, ASH>(h, A2, Bc, Cc, cu[j], cd[j], HAS_Z ? cz[j] : 0.0f, Dv, bias);
             if (ACC) y += co[j];
             bio<T>::st(r_o, vo, (IDX ? oidx[l] : l) * sl_o, y);
-            if (CKPT && (j + 1) % FWD_CKE == 0) store_ckpt(l0 + j + 1);      // l0 is a multiple of PF
+            if (CKPT && (j + 1) % DM_SCAN_CKPT_EVERY == 0) store_ckpt(l0 + j + 1);      // l0 is a multiple of PF
         }
         buf ^= 1;
         stash_bc(buf, nbc);
@@ -251,7 +250,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
             float y = scan_step<N, HAS_Z, SOFTPLUS, ASH>(h, A2, Bc, Cc, ru[j], rd[j], HAS_Z ? rz[j] : 0.0f, Dv, bias);
             if (ACC) y += ro[j];
             bio<T>::st(r_o, vo, (IDX ? oidx[l] : l) * sl_o, y);
-            if (CKPT && (j + 1) % FWD_CKE == 0) store_ckpt(l + 1);
+            if (CKPT && (j + 1) % DM_SCAN_CKPT_EVERY == 0) store_ckpt(l + 1);
         }
     }
 
@@ -268,7 +267,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
 }
 
 constexpr int SCAN_PF = 8;
-static_assert(SCAN_PF % FWD_CKE == 0, "checkpoints fall on fixed positions of a prefetch block");
+static_assert(SCAN_PF % DM_SCAN_CKPT_EVERY == 0, "checkpoints fall on fixed positions of a prefetch block");
 
 template <typename T, typename TBC, int N, bool HAS_Z, bool IDX>
 static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st, dim3 grid) {
@@ -307,12 +306,7 @@ static int launch_fwd(const dm_scan_fwd_args& a, hipStream_t st) {
         if (idx) launch_fwd3<T, TBC, N, false, true>(a, st, grid);
         else launch_fwd3<T, TBC, N, false, false>(a, st, grid);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("dm_selective_scan_fwd: launch failed: %s", hipGetErrorString(e));
-        return DM_ERR_LAUNCH;
-    }
-    return DM_OK;
+    return launch_status("dm_selective_scan_fwd");
 }
 
 template <typename T, typename TBC>

@@ -16,8 +16,7 @@
 // per-head dt is read in the kernel (token order, through the gather table), no [nseq, L, Din] delta tensor exists.
 // 16-bit I/O only (the score tile is rounded to the I/O dtype); fp32 I/O stays on the A-shared scan.  Backward twin: ssd_bwd.hip.
 #include <type_traits>
-#include "dm_common.h"
-#include "ssd_common.h"
+#include "dm_mfma.h"
 
 namespace dm {
 
@@ -36,7 +35,7 @@ constexpr int SSD_PITCH = 20;                     // dwords per staged tile row 
 // there alpha * gamma could underflow while the true factor is O(1)).
 template <typename T>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ssd_fwd_kernel(const dm_ssd_fwd_args p) {
-    using O = ssd_ops<T>;
+    using O = mfma<T>;
     constexpr int ES = (int)sizeof(T);
     __shared__ __attribute__((aligned(16))) float s2_lds[2][SSD_MAXL + 32];    // log2-domain log-decay (prefix sums, ping-pong)
     __shared__ __attribute__((aligned(16))) float dt_lds[SSD_MAXL];
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 
     // ---- every load that does not depend on the decays goes out first: one HBM round trip covers X, B and the dt gather ------
     const int cb = (h * 64 + half * 32 + thf * 16) * ES;                 // byte offset of this lane's 16 staged channels in a row
-    ssd_u32x4 xq[SSD_MAXT][2], bq[SSD_MAXT];
+    u32x4_t xq[SSD_MAXT][2], bq[SSD_MAXT];
 #pragma unroll
     for (int it = 0; it < SSD_MAXT; ++it) {
         const int i = SSD_TILE * it + trow;
@@ -75,12 +74,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_x, ic * sl_x + cb + 16 * q, 0, 0);
-            xq[it][q] = (ssd_u32x4){v[0], v[1], v[2], v[3]};
+            xq[it][q] = (u32x4_t){v[0], v[1], v[2], v[3]};
         }
         const int j = SSD_TILE * it + col;
         const int jc = j < L ? j : L - 1;
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_B, jc * sl_B + kh * 8 * ES, 0, 0);
-        bq[it] = (ssd_u32x4){v[0], v[1], v[2], v[3]};
+        bq[it] = (u32x4_t){v[0], v[1], v[2], v[3]};
     }
 
     // ---- per-position scalars: dt = softplus(raw + bias), log-decay prefix sums, row tables -------------------------------
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 
     // ---- operands resident for the whole sequence ---------------------------------------------------------------------------
     // (gamma .* dt .* B) rows as A-fragments of the off-diagonal score products: lane (row i = col, kh) holds 8 states
-    ssd_u32x4 bfrag[SSD_MAXT];
+    u32x4_t bfrag[SSD_MAXT];
 #pragma unroll
     for (int it = 0; it < SSD_MAXT; ++it) {
         const int i = SSD_TILE * it + col;
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
         for (int w = 0; w < 4; ++w) bfrag[it][w] = O::pack(O::lo(bq[it][w]) * sc, O::hi(bq[it][w]) * sc);
     }
     // X as B-fragments of the output product, keys in accumulator order: slot e of (it, ks) is key 32it + 4kh + 8(2ks + e/4) + e%4
-    ssd_u32x4 xfrag[SSD_MAXT][2];
+    u32x4_t xfrag[SSD_MAXT][2];
     {
         const uint16_t* const ta16 = reinterpret_cast<const uint16_t*>(tile_a);
 #pragma unroll
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
             const bool live = SSD_TILE * it + trow < L;
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                *reinterpret_cast<ssd_u32x4*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = live ? xq[it][q] : (ssd_u32x4){0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4_t*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = live ? xq[it][q] : (u32x4_t){0u, 0u, 0u, 0u};
             __syncthreads();
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
                     const uint32_t lo = ta16[k0 * (2 * SSD_PITCH) + col], hi = ta16[(k0 + 1) * (2 * SSD_PITCH) + col];
                     w4[e2] = lo | (hi << 16);
                 }
-                xfrag[it][ks] = (ssd_u32x4){w4[0], w4[1], w4[2], w4[3]};
+                xfrag[it][ks] = (u32x4_t){w4[0], w4[1], w4[2], w4[3]};
             }
             __syncthreads();
         }
@@ -155,15 +154,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 
     // C rows (the B-operand of the score product: lane (col l, kh) holds C[l][8kh .. +7]) and the unscaled B rows of the diagonal
     // tile are fetched one query tile ahead
-    auto load_cb = [&](int t, ssd_u32x4& c, ssd_u32x4& b) {
+    auto load_cb = [&](int t, u32x4_t& c, u32x4_t& b) {
         const int j = SSD_TILE * t + col;
         const int jc = j < L ? j : L - 1;
         const auto vc = __builtin_amdgcn_raw_buffer_load_b128(r_C, jc * sl_C + kh * 8 * ES, 0, 0);
         const auto vb = __builtin_amdgcn_raw_buffer_load_b128(r_B, jc * sl_B + kh * 8 * ES, 0, 0);
-        c = (ssd_u32x4){vc[0], vc[1], vc[2], vc[3]};
-        b = (ssd_u32x4){vb[0], vb[1], vb[2], vb[3]};
+        c = (u32x4_t){vc[0], vc[1], vc[2], vc[3]};
+        b = (u32x4_t){vb[0], vb[1], vb[2], vb[3]};
     };
-    ssd_u32x4 cnext, bnext;
+    u32x4_t cnext, bnext;
     load_cb(0, cnext, bnext);
 #pragma unroll
     for (int lt = 0; lt < SSD_MAXT; ++lt) {                              // (fully unrolled: every fragment index is a compile-time constant)
@@ -171,10 +170,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
         const int lq = SSD_TILE * lt + col;                              // this lane's query in the score tile (a column of G^T)
         const int lqc = lq < L ? lq : L - 1;
         const float s2l = s2[lqc], mlt = m_of(lt);
-        const ssd_u32x4 craw = cnext, qb = bnext;                         // raw C for the diagonal tile, alpha-scaled for the others
-        const ssd_u32x4 qc = craw;
+        const u32x4_t craw = cnext, qb = bnext;                         // raw C for the diagonal tile, alpha-scaled for the others
+        const u32x4_t qc = craw;
         if (lt + 1 < SSD_MAXT) load_cb(lt + 1, cnext, bnext);
-        ssd_u32x4 zq[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};                // the gate tile of this query tile, in flight under the products
+        u32x4_t zq[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};                // the gate tile of this query tile, in flight under the products
         const int lrow = SSD_TILE * lt + trow;
         const int lrc = lrow < L ? lrow : L - 1;
         if (p.z) {
@@ -182,11 +181,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zr * sl_z + cb + 16 * q, 0, 0);
-                zq[q] = (ssd_u32x4){v[0], v[1], v[2], v[3]};
+                zq[q] = (u32x4_t){v[0], v[1], v[2], v[3]};
             }
         }
         const float alpha = fast_exp2(s2l - mlt);
-        ssd_u32x4 cfrag;
+        u32x4_t cfrag;
 #pragma unroll
         for (int w = 0; w < 4; ++w) cfrag[w] = O::pack(O::lo(qc[w]) * alpha, O::hi(qc[w]) * alpha);
         f32x16 yacc;
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
                 f32x16 g;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-                g = O::mfma(bfrag[it], cfrag, g);                         // rows = keys 32it + 4kh + 8r4 + r, columns = queries
+                g = O::m32(bfrag[it], cfrag, g);                         // rows = keys 32it + 4kh + 8r4 + r, columns = queries
                 const float delta = fast_exp2(mlt - m_of(it + 1));
                 uint32_t wp[8];
 #pragma unroll
@@ -209,8 +208,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const ssd_u32x4 wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                    yacc = O::mfma(wf, xfrag[it][ks], yacc);
+                    const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
+                    yacc = O::m32(wf, xfrag[it][ks], yacc);
                 }
             }
         }
@@ -219,13 +218,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
             const int i = SSD_TILE * lt + col;
             const int ic = i < L ? i : L - 1;
             const float dti = (i < L) ? dt_lds[ic] : 0.0f;
-            ssd_u32x4 bd;
+            u32x4_t bd;
 #pragma unroll
             for (int w = 0; w < 4; ++w) bd[w] = O::pack(O::lo(qb[w]) * dti, O::hi(qb[w]) * dti);
             f32x16 g;
 #pragma unroll
             for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-            g = O::mfma(bd, craw, g);
+            g = O::m32(bd, craw, g);
             uint32_t wp[8];
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
@@ -244,8 +243,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
                 if (it == lt) {
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
-                        const ssd_u32x4 wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                        yacc = O::mfma(wf, xfrag[it][ks], yacc);
+                        const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
+                        yacc = O::m32(wf, xfrag[it][ks], yacc);
                     }
                 }
             }
@@ -253,7 +252,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
         // ---- epilogue of the query tile: + D x, gate, scatter.  yacc[4 r4 + r] = Y[32lt + 4kh + 8 r4 + r][this lane's channel] ----
         if (p.z) {
 #pragma unroll
-            for (int q = 0; q < 2; ++q) *reinterpret_cast<ssd_u32x4*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = zq[q];
+            for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4_t*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = zq[q];
         }
         __syncthreads();
         {
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
             const int orow = oi_lds[lrow];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const ssd_u32x4 v = *reinterpret_cast<const ssd_u32x4*>(&tile_b[trow * SSD_PITCH + thf * 8 + 4 * q]);
+                const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&tile_b[trow * SSD_PITCH + thf * 8 + 4 * q]);
                 __builtin_amdgcn_raw_buffer_store_b128(v, r_o, orow * sl_o + cb + 16 * q, 0, 0);
             }
         }
@@ -319,7 +318,5 @@ extern "C" int dm_ssd_fwd(const dm_ssd_fwd_args* args, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (a.io_dtype == DM_BF16) hipLaunchKernelGGL((ssd_fwd_kernel<bf16_t>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((ssd_fwd_kernel<f16_t>), grid, block, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_ssd_fwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_ssd_fwd");
 }

@@ -24,8 +24,7 @@
 // one product by 1.0 per element).  16 MFMAs and ~160 VALU per pair and orientation.  Tile epilogues turn 8 rows at a time through a 2 KB staging tile so
 // every global access is a 16-byte piece of a row.  The final d dt / dA reverse cumulative sum runs on the whole workgroup
 // (shuffle scans inside the waves, one barrier).  Measured and profiled: DESIGN.md section 3 (K6b), profiles/r02_pmc_scan_kernels.txt.
-#include "dm_common.h"
-#include "ssd_common.h"
+#include "dm_mfma.h"
 
 namespace dm {
 
@@ -58,30 +57,30 @@ __device__ __forceinline__ void wave_lds_sync() {         // make one wave's LDS
 }
 
 // 8 consecutive columns (chunk) of a row of the swizzled [197][64] arrays, as an MFMA operand fragment (rows >= 196: the zero row)
-__device__ __forceinline__ ssd_u32x4 row_frag(const uint8_t* base, int row, int chunk) {
+__device__ __forceinline__ u32x4_t row_frag(const uint8_t* base, int row, int chunk) {
     const int rc = row < SB_MAXL ? row : SB_MAXL;
-    return *reinterpret_cast<const ssd_u32x4*>(base + rc * 128 + ((chunk ^ (rc & 7)) << 4));
+    return *reinterpret_cast<const u32x4_t*>(base + rc * 128 + ((chunk ^ (rc & 7)) << 4));
 }
 // 8 states of a B / C row
-__device__ __forceinline__ ssd_u32x4 bc_frag(const uint8_t* base, int row, int kh) {
+__device__ __forceinline__ u32x4_t bc_frag(const uint8_t* base, int row, int kh) {
     const int rc = row < SB_MAXL ? row : SB_MAXL;
-    return *reinterpret_cast<const ssd_u32x4*>(base + rc * 32 + kh * 16);
+    return *reinterpret_cast<const u32x4_t*>(base + rc * 32 + kh * 16);
 }
 // One-hot selector fragment: slot e (0..7) of this lane holds 1.0, every other slot 0 (e outside 0..7: all zero)
 template <typename T>
-__device__ __forceinline__ ssd_u32x4 one_hot(int e) {
+__device__ __forceinline__ u32x4_t one_hot(int e) {
     constexpr uint32_t ONE = std::is_same<T, bf16_t>::value ? 0x3F80u : 0x3C00u;
     const uint32_t v = (e & 1) ? (ONE << 16) : ONE;
     const int d = e >> 1;
     const bool ok = e >= 0 && e < 8;
-    return (ssd_u32x4){(ok && d == 0) ? v : 0u, (ok && d == 1) ? v : 0u, (ok && d == 2) ? v : 0u, (ok && d == 3) ? v : 0u};
+    return (u32x4_t){(ok && d == 0) ? v : 0u, (ok && d == 1) ? v : 0u, (ok && d == 2) ? v : 0u, (ok && d == 3) ? v : 0u};
 }
 // accumulator tile -> the two K-step fragments (8 positions each, accumulator order) of a 16-bit B-operand
 template <typename O>
-__device__ __forceinline__ void acc_to_frags(const f32x16& d, ssd_u32x4 (&f)[2]) {
+__device__ __forceinline__ void acc_to_frags(const f32x16& d, u32x4_t (&f)[2]) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
-        f[ks] = (ssd_u32x4){O::pack(d[8 * ks], d[8 * ks + 1]), O::pack(d[8 * ks + 2], d[8 * ks + 3]), O::pack(d[8 * ks + 4], d[8 * ks + 5]),
+        f[ks] = (u32x4_t){O::pack(d[8 * ks], d[8 * ks + 1]), O::pack(d[8 * ks + 2], d[8 * ks + 3]), O::pack(d[8 * ks + 4], d[8 * ks + 5]),
                             O::pack(d[8 * ks + 6], d[8 * ks + 7])};
 }
 
@@ -103,7 +102,7 @@ __device__ __forceinline__ float block_prefix_sum(float v, int lane, int w, floa
 
 template <typename T>
 __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void ssd_bwd_kernel(const dm_ssd_bwd_args p) {
-    using O = ssd_ops<T>;
+    using O = mfma<T>;
     constexpr int ES = (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     float* const tab = reinterpret_cast<float*>(lds + SB_TABS);
@@ -153,7 +152,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     // phase 1 role: wave w moves the 16-byte chunks w and w + 4 of every row; lane rows r = lane + 64 j
     float dtv = 0.0f, sg0 = 0.0f;
     int zr0 = 0, orow0 = 0;
-    ssd_u32x4 bq[2], cq[2];
+    u32x4_t bq[2], cq[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {                                                 // B / C: two 16-byte chunks per row, two rows per thread
         const int e = tid + SB_THREADS * i;
@@ -161,13 +160,13 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         const int rc = r < L ? r : L - 1;
         const auto b = __builtin_amdgcn_raw_buffer_load_b128(r_B, rc * sl_B + hf * 16, 0, 0);
         const auto c = __builtin_amdgcn_raw_buffer_load_b128(r_C, rc * sl_C + hf * 16, 0, 0);
-        bq[i] = (ssd_u32x4){b[0], b[1], b[2], b[3]};
-        cq[i] = (ssd_u32x4){c[0], c[1], c[2], c[3]};
+        bq[i] = (u32x4_t){b[0], b[1], b[2], b[3]};
+        cq[i] = (u32x4_t){c[0], c[1], c[2], c[3]};
     }
     const int pc = tid < L ? tid : L - 1;
     if (zidx) { zr0 = zidx[pc]; orow0 = oidx[pc]; } else { zr0 = pc; orow0 = pc; }
     int zrow[4], drow[4];
-    ssd_u32x4 xq4[2][4], dq4[2][4], zq4[2][4];
+    u32x4_t xq4[2][4], dq4[2][4], zq4[2][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = lane + 64 * j;
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const auto xq = __builtin_amdgcn_raw_buffer_load_b128(r_x, rc * sl_x + hb + (w + 4 * m) * 16, 0, 0);
-            xq4[m][j] = (ssd_u32x4){xq[0], xq[1], xq[2], xq[3]};
+            xq4[m][j] = (u32x4_t){xq[0], xq[1], xq[2], xq[3]};
         }
     }
     // level 2: through the indices
@@ -189,11 +188,11 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         for (int m = 0; m < 2; ++m) {
             const int cb = hb + (w + 4 * m) * 16;
             const auto dq = __builtin_amdgcn_raw_buffer_load_b128(r_do, drow[j] * sl_do + cb, 0, 0);
-            dq4[m][j] = (ssd_u32x4){dq[0], dq[1], dq[2], dq[3]};
-            zq4[m][j] = (ssd_u32x4){0u, 0u, 0u, 0u};
+            dq4[m][j] = (u32x4_t){dq[0], dq[1], dq[2], dq[3]};
+            zq4[m][j] = (u32x4_t){0u, 0u, 0u, 0u};
             if (p.z) {
                 const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zrow[j] * sl_z + cb, 0, 0);
-                zq4[m][j] = (ssd_u32x4){v[0], v[1], v[2], v[3]};
+                zq4[m][j] = (u32x4_t){v[0], v[1], v[2], v[3]};
             }
         }
     // B / C into LDS (level 1 has landed by the time the dt value is needed)
@@ -202,9 +201,9 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         const int e = tid + SB_THREADS * i;
         const int r = e >> 1, hf = e & 1;
         if (r < SB_ROWS) {
-            const ssd_u32x4 zero4 = {0u, 0u, 0u, 0u};
-            *reinterpret_cast<ssd_u32x4*>(lds + SB_BS + r * 32 + hf * 16) = r < L ? bq[i] : zero4;
-            *reinterpret_cast<ssd_u32x4*>(lds + SB_CS + r * 32 + hf * 16) = r < L ? cq[i] : zero4;
+            const u32x4_t zero4 = {0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4_t*>(lds + SB_BS + r * 32 + hf * 16) = r < L ? bq[i] : zero4;
+            *reinterpret_cast<u32x4_t*>(lds + SB_CS + r * 32 + hf * 16) = r < L ? cq[i] : zero4;
         }
     }
     // per-position scalars (thread t <-> position t)
@@ -250,9 +249,9 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         for (int j = 0; j < 4; ++j) {
             const int r = lane + 64 * j;
             if (r < SB_ROWS) {
-                ssd_u32x4 xv = {0u, 0u, 0u, 0u}, gv = {0u, 0u, 0u, 0u};
+                u32x4_t xv = {0u, 0u, 0u, 0u}, gv = {0u, 0u, 0u, 0u};
                 if (r < L) {
-                    const ssd_u32x4 xq = xq4[m][j], dq = dq4[m][j], zq = zq4[m][j];
+                    const u32x4_t xq = xq4[m][j], dq = dq4[m][j], zq = zq4[m][j];
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         float g0 = O::lo(dq[d]), g1 = O::hi(dq[d]);
@@ -266,8 +265,8 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                     }
                 }
                 const int so = r * 128 + ((ck ^ (r & 7)) << 4);
-                *reinterpret_cast<ssd_u32x4*>(lds + SB_XS + so) = xv;
-                *reinterpret_cast<ssd_u32x4*>(lds + SB_GS + so) = gv;
+                *reinterpret_cast<u32x4_t*>(lds + SB_XS + so) = xv;
+                *reinterpret_cast<u32x4_t*>(lds + SB_GS + so) = gv;
             }
         }
     }
@@ -280,8 +279,8 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // selectors: a [positions x 64 channels] row-major fragment set times these = the 32-channel half nt in accumulator layout
     // (K-step j of the half: channel 32 nt + q sits in slot q - 16 j - 8 kh); states likewise (16 of them, columns 16-31 empty)
-    const ssd_u32x4 selx[2] = {one_hot<T>(q - 8 * kh), one_hot<T>(q - 16 - 8 * kh)};
-    const ssd_u32x4 sel16 = one_hot<T>(q < 16 ? q - 8 * kh : -1);
+    const u32x4_t selx[2] = {one_hot<T>(q - 8 * kh), one_hot<T>(q - 16 - 8 * kh)};
+    const u32x4_t sel16 = one_hot<T>(q < 16 ? q - 8 * kh : -1);
     // role of the wave: waves land on SIMD (w & 3); the T waves carry the heavier epilogue, so odd heads swap the roles and the two
     // workgroups a CU holds put one T and one N wave on every SIMD
     const int wr = (w + 2 * (int)(blockIdx.x & 1)) & 3;
@@ -293,23 +292,23 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             const int lt = (wr == 0) ? (pass == 0 ? 6 : pass == 1 ? 3 : pass == 2 ? 2 : 0) : (pass == 0 ? 5 : pass == 1 ? 4 : pass == 2 ? 1 : -1);
             if (lt < 0 || lt >= nt_l) continue;
             const int ql = SB_TILE * lt + q;
-            const ssd_u32x4 cB = bc_frag(lds + SB_CS, ql, kh);
-            ssd_u32x4 gB[4];
+            const u32x4_t cB = bc_frag(lds + SB_CS, ql, kh);
+            u32x4_t gB[4];
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) gB[ks] = row_frag(lds + SB_GS, ql, 2 * ks + kh);
             const float s2q = S2[ql], aq = ALPHA[ql], mlt = m_of(lt);
-            ssd_u32x4 zq4[4], dq4[4];                                             // the epilogue's z / dout pieces, in flight under the products
+            u32x4_t zq4[4], dq4[4];                                             // the epilogue's z / dout pieces, in flight under the products
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int l = SB_TILE * lt + 8 * r4 + row8;
                 const int lc = l < L ? l : L - 1;
-                zq4[r4] = (ssd_u32x4){0u, 0u, 0u, 0u};
-                dq4[r4] = (ssd_u32x4){0u, 0u, 0u, 0u};
+                zq4[r4] = (u32x4_t){0u, 0u, 0u, 0u};
+                dq4[r4] = (u32x4_t){0u, 0u, 0u, 0u};
                 if (p.dz) {
                     const auto zq = __builtin_amdgcn_raw_buffer_load_b128(r_z, (int)zi[lc] * sl_z + hb + c8 * 16, 0, 0);
                     const auto dq = __builtin_amdgcn_raw_buffer_load_b128(r_do, (int)oi[lc] * sl_do + hb + c8 * 16, 0, 0);
-                    zq4[r4] = (ssd_u32x4){zq[0], zq[1], zq[2], zq[3]};
-                    dq4[r4] = (ssd_u32x4){dq[0], dq[1], dq[2], dq[3]};
+                    zq4[r4] = (u32x4_t){zq[0], zq[1], zq[2], zq[3]};
+                    dq4[r4] = (u32x4_t){dq[0], dq[1], dq[2], dq[3]};
                 }
             }
             f32x16 Y0 = zero16, Y1 = zero16, dC = zero16;
@@ -317,19 +316,19 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll 1
             for (int it = 0; it <= lt; ++it) {
                 const int ki = SB_TILE * it + q;
-                const ssd_u32x4 bA = bc_frag(lds + SB_BS, ki, kh);
-                f32x16 g = O::mfma(bA, cB, zero16);                               // G[query][key]: keys 32it + 4kh + 8r4 + r in registers
-                ssd_u32x4 xA[4];
+                const u32x4_t bA = bc_frag(lds + SB_BS, ki, kh);
+                f32x16 g = O::m32(bA, cB, zero16);                               // G[query][key]: keys 32it + 4kh + 8r4 + r in registers
+                u32x4_t xA[4];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) xA[ks] = row_frag(lds + SB_XS, ki, 2 * ks + kh);
                 f32x16 rr = zero16;
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) rr = O::mfma(xA[ks], gB[ks], rr);   // R = gY . X
+                for (int ks = 0; ks < 4; ++ks) rr = O::m32(xA[ks], gB[ks], rr);   // R = gY . X
                 // X and B of the key tile with the keys in the K slots (accumulator order): selector products
-                ssd_u32x4 xf0[2], xf1[2], bf[2];
-                acc_to_frags<O>(O::mfma(xA[1], selx[1], O::mfma(xA[0], selx[0], zero16)), xf0);
-                acc_to_frags<O>(O::mfma(xA[3], selx[1], O::mfma(xA[2], selx[0], zero16)), xf1);
-                acc_to_frags<O>(O::mfma(bA, sel16, zero16), bf);
+                u32x4_t xf0[2], xf1[2], bf[2];
+                acc_to_frags<O>(O::m32(xA[1], selx[1], O::m32(xA[0], selx[0], zero16)), xf0);
+                acc_to_frags<O>(O::m32(xA[3], selx[1], O::m32(xA[2], selx[0], zero16)), xf1);
+                acc_to_frags<O>(O::m32(bA, sel16, zero16), bf);
                 const int kb = SB_TILE * it + 4 * kh;
                 float md[16];                                                     // M[query][key] * dt_key
                 if (it < lt) {
@@ -359,11 +358,11 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const ssd_u32x4 wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                    const ssd_u32x4 df = {dp[4 * ks], dp[4 * ks + 1], dp[4 * ks + 2], dp[4 * ks + 3]};
-                    Y0 = O::mfma(wf, xf0[ks], Y0);
-                    Y1 = O::mfma(wf, xf1[ks], Y1);
-                    dC = O::mfma(df, bf[ks], dC);
+                    const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
+                    const u32x4_t df = {dp[4 * ks], dp[4 * ks + 1], dp[4 * ks + 2], dp[4 * ks + 3]};
+                    Y0 = O::m32(wf, xf0[ks], Y0);
+                    Y1 = O::m32(wf, xf1[ks], Y1);
+                    dC = O::m32(df, bf[ks], dC);
                 }
             }
             rs += __shfl_xor(rs, 32);
@@ -391,10 +390,10 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 wave_lds_sync();
                 const int l = SB_TILE * lt + 8 * r4 + row8;
                 if (p.dz && l < L) {
-                    const ssd_u32x4 xq = row_frag(lds + SB_XS, l, c8);
+                    const u32x4_t xq = row_frag(lds + SB_XS, l, c8);
                     const int zr = zi[l];
-                    const ssd_u32x4 zq = zq4[r4], dq = dq4[r4];
-                    ssd_u32x4 o;
+                    const u32x4_t zq = zq4[r4], dq = dq4[r4];
+                    u32x4_t o;
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         float res[2];
@@ -421,8 +420,8 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             if (it < 0 || it >= nt_l) continue;
             const int ki = SB_TILE * it + q;
             const int kic = ki < SB_TAB ? ki : SB_TAB - 1;
-            const ssd_u32x4 bB = bc_frag(lds + SB_BS, ki, kh);
-            ssd_u32x4 xB[4];
+            const u32x4_t bB = bc_frag(lds + SB_BS, ki, kh);
+            u32x4_t xB[4];
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) xB[ks] = row_frag(lds + SB_XS, ki, 2 * ks + kh);
             const float dtk = DT[kic], gamk = GAM[kic], s2k = S2[kic], mnext = S2[SB_TILE * it + SB_TILE - 1];
@@ -431,18 +430,18 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll 1
             for (int lt = it; lt < nt_l; ++lt) {
                 const int qrow = SB_TILE * lt + q;
-                const ssd_u32x4 cA = bc_frag(lds + SB_CS, qrow, kh);
-                f32x16 g = O::mfma(cA, bB, zero16);                               // G[query][key]: queries 32lt + 4kh + 8r4 + r in registers
-                ssd_u32x4 gA[4];
+                const u32x4_t cA = bc_frag(lds + SB_CS, qrow, kh);
+                f32x16 g = O::m32(cA, bB, zero16);                               // G[query][key]: queries 32lt + 4kh + 8r4 + r in registers
+                u32x4_t gA[4];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) gA[ks] = row_frag(lds + SB_GS, qrow, 2 * ks + kh);
                 f32x16 rr = zero16;
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) rr = O::mfma(gA[ks], xB[ks], rr);
-                ssd_u32x4 gf0[2], gf1[2], cf[2];                                   // gY and C of the query tile with the queries in the K slots
-                acc_to_frags<O>(O::mfma(gA[1], selx[1], O::mfma(gA[0], selx[0], zero16)), gf0);
-                acc_to_frags<O>(O::mfma(gA[3], selx[1], O::mfma(gA[2], selx[0], zero16)), gf1);
-                acc_to_frags<O>(O::mfma(cA, sel16, zero16), cf);
+                for (int ks = 0; ks < 4; ++ks) rr = O::m32(gA[ks], xB[ks], rr);
+                u32x4_t gf0[2], gf1[2], cf[2];                                   // gY and C of the query tile with the queries in the K slots
+                acc_to_frags<O>(O::m32(gA[1], selx[1], O::m32(gA[0], selx[0], zero16)), gf0);
+                acc_to_frags<O>(O::m32(gA[3], selx[1], O::m32(gA[2], selx[0], zero16)), gf1);
+                acc_to_frags<O>(O::m32(cA, sel16, zero16), cf);
                 const int qb = SB_TILE * lt + 4 * kh;
                 float mf[16];                                                     // M[query][key] (without dt)
                 if (lt > it) {
@@ -471,11 +470,11 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 }
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const ssd_u32x4 wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                    const ssd_u32x4 df = {dp[4 * ks], dp[4 * ks + 1], dp[4 * ks + 2], dp[4 * ks + 3]};
-                    X0 = O::mfma(wf, gf0[ks], X0);
-                    X1 = O::mfma(wf, gf1[ks], X1);
-                    dB = O::mfma(df, cf[ks], dB);
+                    const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
+                    const u32x4_t df = {dp[4 * ks], dp[4 * ks + 1], dp[4 * ks + 2], dp[4 * ks + 3]};
+                    X0 = O::m32(wf, gf0[ks], X0);
+                    X1 = O::m32(wf, gf1[ks], X1);
+                    dB = O::m32(df, cf[ks], dB);
                 }
             }
             cv += __shfl_xor(cv, 32);
@@ -503,8 +502,8 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 wave_lds_sync();
                 const int l = SB_TILE * it + 8 * r4 + row8;
                 if (l < L) {
-                    const ssd_u32x4 gq = row_frag(lds + SB_GS, l, c8);
-                    ssd_u32x4 o;
+                    const u32x4_t gq = row_frag(lds + SB_GS, l, c8);
+                    u32x4_t o;
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         const float u0 = (d < 2 ? ua[2 * d] : ub[2 * (d - 2)]) + Dh * O::lo(gq[d]);
@@ -575,7 +574,6 @@ extern "C" int dm_ssd_bwd(const dm_ssd_bwd_args* args, void* stream) {
     }
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(a.nheads, a.nseq), block(SB_THREADS);
-    hipError_t e;
     // the dynamic-LDS limit of a kernel is a per-DEVICE attribute: set it once per (device, instantiation), not once per process
     // (a process that launches on a second GPU would otherwise fail there with 79 KB of dynamic LDS -- ADVICE r2)
     static bool reserved[2][64] = {};
@@ -590,7 +588,5 @@ extern "C" int dm_ssd_bwd(const dm_ssd_bwd_args* args, void* stream) {
     }
     if (which == 0) hipLaunchKernelGGL((ssd_bwd_kernel<bf16_t>), grid, block, SB_LDS_BYTES, st, a);
     else hipLaunchKernelGGL((ssd_bwd_kernel<f16_t>), grid, block, SB_LDS_BYTES, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dm_ssd_bwd: launch failed: %s", hipGetErrorString(e)); return DM_ERR_LAUNCH; }
-    return DM_OK;
+    return launch_status("dm_ssd_bwd");
 }

@@ -17,7 +17,7 @@ from ._lib import (DM_BF16, DM_F16, DM_F32, DM_FLAG_A_SHARED, DM_FLAG_DELTA_ACTI
                    dm_conv_fwd_args, dm_conv_xproj_bwd_args, dm_conv_xproj_fwd_args, dm_diffusion_step_args, dm_ln_mod_args, dm_ssd_bwd_args, dm_ssd_fwd_args, dm_merge_args, dm_gate_bwd_args, dm_dtproj_args, dm_scan_bwd_args, dm_scan_fwd_args, dm_gemm_args, dm_repack_args, dm_training_loss_args)
 
 _DT = {torch.float32: DM_F32, torch.bfloat16: DM_BF16, torch.float16: DM_F16}
-SCAN_CKPT_EVERY = 4          # forward checkpoint spacing = backward sub-chunk length (csrc/scan_bwd_impl.h BWD_SUB)
+SCAN_CKPT_EVERY = _lib.DM_SCAN_CKPT_EVERY          # forward checkpoint spacing = backward sub-chunk length
 
 
 def union_length(intervals):
@@ -872,7 +872,7 @@ def gemm_large(a, b, out=None):
     return out
 
 
-LN_ROWS_PER_BLOCK = 28   # DM_LN_ROWS_PER_BLOCK
+LN_ROWS_PER_BLOCK = _lib.DM_LN_ROWS_PER_BLOCK
 LN_SMALL_ROWS = int(os.environ.get("DIFFMA_LN_SMALL_ROWS", "4"))     # rows per partial-sum group of the backward when a launch has few rows; 0: always 28
 
 

@@ -172,6 +172,7 @@ int dm_grads_nonfinite(const dm_adamw_args *args, void *stream);
  * the precision the I/O tensors already have).  The buffer is private to the forward / backward pair of one build.
  * last_state (optional): final h, fp32, layout [s][n][d].
  * ---------------------------------------------------------------------------------------------- */
+#define DM_SCAN_CKPT_EVERY 4 /* the one checkpoint spacing the kernels are built for = the backward's sub-chunk length; the value ckpt_every must hold */
 typedef struct {
     int32_t nseq, dim, seqlen, dstate;
     int32_t ngroups;         /* B/C groups over the channel axis (DiffMa: 1)           */

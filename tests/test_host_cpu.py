@@ -525,6 +525,59 @@ def test_fused_optimizer_predicate_and_state_layout():
     assert ctypes.sizeof(_lib.dm_adamw_tensor) == 56                                   # 7 x 8 bytes: the rows FusedAdamWEMA writes as int64
 
 
+def _header_text_without_comments():
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "diffma_hip.h")) as f:
+        return re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+
+
+def test_binding_argtypes_follow_every_prototype():
+    """_lib derives each function's argtypes from its prototype in include/diffma_hip.h (no list of names to keep up): for every
+    prototype of the header the arity is the prototype's, a pointer parameter is c_void_p and an integer parameter is its own
+    ctypes type.  Needs no built library."""
+    import ctypes
+    import re
+
+    from diffma_amd import _lib
+
+    protos = re.findall(r"\b(dm_\w+)\s*\(([^()]*)\)\s*;", _header_text_without_comments())
+    assert len(protos) >= 60 and {n for n, _ in protos} == set(_lib.ARGTYPES) == set(_lib.EXPORTED_SYMBOLS)
+    ints = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+    for name, params in protos:
+        params = [] if params.strip() in ("void", "") else [p.strip() for p in params.split(",")]
+        got = _lib.ARGTYPES[name]
+        assert len(got) == len(params), (name, params, got)
+        for p, t in zip(params, got):
+            if "*" in p:
+                assert t is ctypes.c_void_p, (name, p, t)
+            else:
+                assert t is ints[p.split()[0]], (name, p, t)
+
+
+def test_binding_exposes_every_constant_of_the_header():
+    """Every DM_FLAG_*, dtype and DM_ERR_* name of include/diffma_hip.h is a module attribute of _lib with the header's value
+    (they were typed in by hand before), and so are the integer #defines."""
+    import re
+
+    from diffma_amd import _lib
+
+    text = _header_text_without_comments()
+    names = set(re.findall(r"\b(DM_FLAG_\w+|DM_ERR_\w+|DM_OK|DM_F32|DM_BF16|DM_F16)\b", text))
+    assert len([n for n in names if n.startswith("DM_FLAG_")]) >= 10 and len([n for n in names if n.startswith("DM_ERR_")]) >= 5
+    for n in names:
+        m = re.search(r"\b%s\s*=\s*(-?\d+)" % n, text)
+        assert m, n
+        assert getattr(_lib, n) == int(m.group(1)), n
+    defines = dict(re.findall(r"^#define\s+(DM_\w+)\s+(\d+)\s*$", text, flags=re.M))
+    assert {"DM_ABI_VERSION", "DM_LN_ROWS_PER_BLOCK", "DM_SCAN_CKPT_EVERY"} <= set(defines)
+    for n, v in defines.items():
+        assert getattr(_lib, n) == int(v), n
+    assert not hasattr(_lib, "DIFFMA_HIP_H")                                            # the include guard is not a constant
+    flags = [getattr(_lib, n) for n in names if n.startswith("DM_FLAG_")]
+    assert len(set(flags)) == len(flags) and all(f & (f - 1) == 0 for f in flags)       # distinct single bits
+
+
 def test_graph_train_setting_true_false_auto():
     """train.graph_train_decision: `graph_train: auto` replays the step from a hipGraph exactly where the reference's own configuration
     sits (config/brain.yaml: one sample per GPU) and leaves large batches, gradient accumulation, fp16 and the CPU alone; booleans and
