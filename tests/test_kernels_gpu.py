@@ -3,6 +3,7 @@
 Tolerances (SURVEY.md 8c): fp32 I/O rtol 1e-4 / atol 1e-5 vs the fp64 recurrence; bf16 I/O 3e-2 / 5e-2;
 fp16 3e-3 / 5e-3.  Integer work (row reindexing) is bit-exact.
 """
+import math
 import os
 import pytest
 import torch
@@ -26,6 +27,31 @@ def _inputs(S, L, Dm, N, dtype, seed, dev, with_z=True):
     Cm = torch.randn(S, L, N, generator=g)
     Dp = torch.randn(Dm, generator=g)
     bias = torch.randn(Dm, generator=g) * 0.5
+    cast = lambda t: None if t is None else t.to(dtype)
+    host = dict(u=cast(u), delta=cast(delta), z=cast(z), A=A, B=cast(Bm), C=cast(Cm), D=Dp, bias=bias)
+    devd = {k: (None if v is None else v.to(dev)) for k, v in host.items()}
+    return host, devd
+
+
+def _inputs_long_memory(S, L, Dm, N, dtype, seed, dev, with_z=True, a_shared=False):
+    """_inputs where the state remembers, as the model initialises it (mamba.py / mamba2.py: A in [-16, -1], dt in [1e-3, 1e-1]):
+    A[d, n] = -(n + 1) c_d with c_d log-uniform in [0.01, 1] (a_shared: A[d, :] = -16 c_d, one decay per channel), and a per-channel dt
+    level log-uniform in [1e-3, 1e-1] times exp(0.3 randn) per step.  dt arrives as delta + bias BEFORE the softplus (bias = the
+    level's pre-activation, delta the rest, rounded to the dtype), so the in-kernel softplus is still what runs.  A slow channel keeps
+    e^(-0.01 * 1e-3 * 196) of state 0 over 196 steps; _inputs keeps e^-200."""
+    g = torch.Generator().manual_seed(seed)
+    u = torch.randn(S, L, Dm, generator=g)
+    z = torch.randn(S, L, Dm, generator=g) if with_z else None
+    c = torch.exp(torch.rand(Dm, generator=g) * math.log(100.0)) * 0.01
+    A = -16.0 * c[:, None].expand(Dm, N).contiguous() if a_shared else -(torch.arange(N) + 1.0)[None, :] * c[:, None]
+    level = torch.exp(torch.rand(Dm, generator=g) * math.log(100.0)) * 1e-3
+    dt = level * torch.exp(0.3 * torch.randn(S, L, Dm, generator=g))
+    inv = lambda t: torch.log(torch.expm1(t.double())).float()                  # softplus^-1
+    bias = inv(level)
+    delta = inv(dt) - bias
+    Bm = torch.randn(S, L, N, generator=g)
+    Cm = torch.randn(S, L, N, generator=g)
+    Dp = torch.randn(Dm, generator=g)
     cast = lambda t: None if t is None else t.to(dtype)
     host = dict(u=cast(u), delta=cast(delta), z=cast(z), A=A, B=cast(Bm), C=cast(Cm), D=Dp, bias=bias)
     devd = {k: (None if v is None else v.to(dev)) for k, v in host.items()}
@@ -101,6 +127,77 @@ def test_scan_fwd_chunk_parallel_variant(gpu, dtype, L, Dm, with_z):
                                            cm(host["B"])[..., :n], cm(host["C"])[..., :n], None, z=None,
                                            delta_bias=host["bias"].double(), delta_softplus=True, return_last_state=True)
                 torch.testing.assert_close(ckpt[s, c].cpu().double().T, hl[0], rtol=1e-4, atol=1e-5 * max(1.0, hl.abs().max().item()))
+
+
+def _ckpt_states(ckpt, N, Dm):
+    """The checkpoint buffer as fp32 states [S, chunk, N, Dm]: fp32 as stored; the packed bf16 form [S, chunk, N/8 * Dm, 4] int32 holds
+    word w of (group g, channel d) = states 8 g + 2 w (low half) and 8 g + 2 w + 1 (high half) (csrc/scan_fwd_impl.h store_slot)."""
+    if ckpt.dtype != torch.int32:
+        return ckpt.float()
+    S, nck = ckpt.shape[:2]
+    w = ckpt.view(S, nck, N // 8, Dm, 4)
+    lo, hi = (w << 16).view(torch.float32), (w & -65536).view(torch.float32)
+    return torch.stack([lo, hi], -1).permute(0, 1, 2, 4, 5, 3).reshape(S, nck, N, Dm)
+
+
+def _oracle_states(host, s):
+    """fp64 state after every step of sequence s, [L, Dm, N]: h_l = exp(dt_l A) h_{l-1} + dt_l u_l B_l, dt = softplus(delta + bias)."""
+    from oracle.mamba_ref import softplus_ref
+
+    d64 = lambda t: t[s].float().double()
+    dt = softplus_ref(d64(host["delta"]) + host["bias"].double())
+    dA = torch.exp(dt[:, :, None] * host["A"].double()[None])
+    dBu = (dt * d64(host["u"]))[:, :, None] * d64(host["B"])[:, None, :]
+    h, hs = torch.zeros_like(dA[0]), []
+    for l in range(dt.shape[0]):
+        h = dA[l] * h + dBu[l]
+        hs.append(h)
+    return torch.stack(hs)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("L", [196, 183])
+def test_scan_fwd_chunk_parallel_long_memory(gpu, dtype, L):
+    """The chunk-parallel forward with checkpoints on _inputs_long_memory, where the carry folded across the 14 wave chunks is O(1)
+    instead of 1e-10: outputs at the tolerances of the file, and EVERY checkpoint slot (49 at L = 196: the state entering every
+    4-step sub-chunk, so all 14 chunk entries and every slot between them; slot 0 = the final state) of the first and the last
+    sequence against the fp64 state.  fp32 checkpoints (fp32 and fp16 I/O): rtol 1e-4 / atol 1e-5 max|h| as in the tests above.
+    Packed bf16 checkpoints: the kernel rounds its fp32 state once (v_cvt_pk_bf16_f32), so u |h| + (1 + u) x that fp32 tolerance,
+    u = 2^-8 -- the oracle state rounded to the format, give or take the fp32 error that can move it across a rounding boundary."""
+    from diffma_amd import hip_ops
+    from oracle.mamba_ref import selective_scan_ref
+
+    Bsz, ndir, N, Dm = 2, 3, 16, 128
+    S = Bsz * ndir
+    host, d = _inputs_long_memory(S, L, Dm, N, dtype, seed=L + Dm, dev=gpu, with_z=False)
+    g = torch.Generator().manual_seed(9)
+    zsrc = torch.randn(Bsz, L, Dm, generator=g).to(dtype)
+    perms = torch.stack([torch.arange(L)] + [torch.randperm(L, generator=g) for _ in range(ndir - 1)]).int()
+    operms = torch.stack([torch.randperm(L, generator=g) for _ in range(ndir)]).int()
+    ckpt = hip_ops.alloc_scan_ckpt(S, L, N, Dm, dtype, gpu).zero_()
+    out = hip_ops.scan_fwd(d["u"], d["delta"], d["A"], d["B"], d["C"], d["D"], zsrc.to(gpu), d["bias"], True, z_row_index=perms.to(gpu),
+                           out_row_index=operms.to(gpu), batch_per_dir=Bsz, ckpt=ckpt, variant="chunked")
+    torch.cuda.synchronize()
+    out = out.float().cpu()
+    got_h = _ckpt_states(ckpt, N, Dm).cpu().double()
+    rtol, atol = TOL[dtype]
+    K = hip_ops.SCAN_CKPT_EVERY
+    for s in range(S):
+        k, b = divmod(s, Bsz)
+        cm = lambda t: t[s:s + 1].float().permute(0, 2, 1).double()
+        zz = zsrc[b][perms[k].long()].float().T[None].double()
+        ref, last = selective_scan_ref(cm(host["u"]), cm(host["delta"]), host["A"].double(), cm(host["B"]), cm(host["C"]), host["D"].double(),
+                                       z=zz, delta_bias=host["bias"].double(), delta_softplus=True, return_last_state=True)
+        torch.testing.assert_close(out[s][operms[k].long()].double(), ref[0].T, rtol=rtol, atol=atol * max(1.0, ref.abs().max().item()))
+        if s in (0, S - 1):
+            hs = _oracle_states(host, s)
+            assert float((hs[-1] - last[0]).abs().max()) <= 1e-12 * float(last.abs().max())          # the restatement is the oracle's
+            for c in range(hip_ops.scan_nchunk(L, K)):
+                want = hs[(c * K if c else L) - 1].T                                                    # [N, Dm]
+                tol32 = 1e-4 * want.abs() + 1e-5 * max(1.0, float(want.abs().max()))
+                tol = tol32 if ckpt.dtype != torch.int32 else 2.0 ** -8 * want.abs() + (1 + 2.0 ** -8) * tol32
+                err = (got_h[s, c] - want).abs()
+                assert bool((err <= tol).all()), (s, c, float((err / tol).max()))
 
 
 @pytest.mark.parametrize("softplus,with_z", [(False, True), (True, False), (False, False)])
@@ -389,14 +486,17 @@ def _grads_to_cpu(*leaves):
 
 
 def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bsz=None, a_shared=False, dout_per_seq=False,
-                   variant="sequential"):
+                   variant="sequential", long_memory=False):
     """a_shared: A[d, :] is one value per channel and the kernels run their DM_FLAG_A_SHARED form (one exp per channel-step, the
     Mamba-2 call pattern); dout_per_seq: the incoming gradient is per direction [S, L, Dm] in token order, read through
     out_row_index (DM_FLAG_DOUT_PER_SEQ) instead of one merged gradient per batch element."""
     from diffma_amd import hip_ops
     from oracle.mamba_ref import selective_scan_ref
 
-    host, d = _inputs(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=with_z and not indexed)
+    if long_memory:
+        host, d = _inputs_long_memory(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=with_z and not indexed, a_shared=a_shared)
+    else:
+        host, d = _inputs(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=with_z and not indexed)
     if a_shared:
         host["A"] = host["A"][:, :1].expand(Dm, N).contiguous()
         d["A"] = host["A"].to(gpu)
@@ -557,6 +657,21 @@ def test_scan_bwd_variants_agree_and_default_choice(gpu):
     rb = hip_ops.scan_bwd(d["u"], d["delta"], d["A"], d["B"], d["C"], d["D"], d["z"], d["bias"], dout, ckpt, True)      # library's choice: chunked
     for name, x0, x1 in zip(("du", "ddelta", "dz", "dB", "dC", "dA", "dD", "dbias"), ra, rb):
         torch.testing.assert_close(x1, x0, rtol=2e-4, atol=2e-5 * max(1.0, x0.abs().max().item()), msg=lambda m, n=name: f"{n}: {m}")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("variant", ["sequential", "chunked"])
+@pytest.mark.parametrize("S,L,kw", [(3, 196, dict(indexed=True, Bsz=1)), (3, 183, dict())], ids=["196-indexed", "183"])
+def test_scan_bwd_long_memory(gpu, dtype, variant, S, L, kw):
+    """_scan_bwd_case, unchanged checks and tolerances, on _inputs_long_memory: the chunk fold, the checkpoint recompute and the
+    dA / d delta reverse sums carry O(1) state over the whole sequence (with _inputs, whatever crosses two chunks is 1e-10)."""
+    _scan_bwd_case(gpu, dtype, S, L, 128, 16, seed=11 * L, variant=variant, long_memory=True, **kw)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_scan_bwd_long_memory_a_shared_dout_per_seq(gpu, dtype):
+    """The Mamba-2 call pattern (one decay per channel in [-16, -0.16], per-direction gradients) where the state remembers."""
+    _scan_bwd_case(gpu, dtype, 3, 196, 128, 16, seed=1961, indexed=True, Bsz=1, a_shared=True, dout_per_seq=True, variant="chunked", long_memory=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -899,7 +1014,7 @@ def test_dtproj_softplus_matches_torch(gpu, dtype, M, Dm, R, P):
     torch.testing.assert_close(delta.cpu().double(), ref, rtol=rtol, atol=atol)
 
 
-def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed):
+def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed, long_memory=False):
     """The DiffMa mixer's call pattern after the hoists: no z, row-index tables, delta already activated (DM_FLAG_DELTA_ACTIVATED),
     the pre-gated gradient shared by the directions.  Forward and backward against fp64 autograd of the oracle run on the SAME
     activated delta; ddelta / dbias must be the gradients of the RAW pre-activation, i.e. times 1 - exp(-delta)."""
@@ -907,7 +1022,7 @@ def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed):
     from oracle.mamba_ref import selective_scan_ref
 
     N, S = 16, ndir * Bsz
-    host, d = _inputs(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=False)
+    host, d = (_inputs_long_memory if long_memory else _inputs)(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=False)
     g = torch.Generator().manual_seed(seed + 1)
     act = torch.nn.functional.softplus(host["delta"].float() + host["bias"]).to(dtype)      # what dm_dtproj_softplus_fwd would hand over
     perm = torch.stack([torch.randperm(L, generator=g) for _ in range(ndir)]).int()
@@ -960,6 +1075,13 @@ def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed):
                                                    (2, 196, 128, 3, "chunked"), (1, 100, 200, 3, "chunked"), (2, 49, 128, 3, "chunked")])
 def test_scan_hoisted_call_pattern_matches_oracle_autograd(gpu, dtype, Bsz, L, Dm, ndir, variant):
     _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed=7 * L + Dm)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("variant", ["sequential", "chunked"])
+def test_scan_hoisted_call_pattern_long_memory(gpu, dtype, variant):
+    """_hoisted_scan_case at L = 196 on _inputs_long_memory: the same checks and tolerances with the state carried across chunks."""
+    _hoisted_scan_case(gpu, dtype, 1, 196, 128, 3, variant, seed=1960, long_memory=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
