@@ -4,6 +4,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/diffma_hip.h"
 
 namespace dm {
@@ -36,6 +37,18 @@ static inline int launch_status(const char* who) {
     if (e == hipSuccess) return DM_OK;
     set_error("%s: launch failed: %s", who, hipGetErrorString(e));
     return DM_ERR_LAUNCH;
+}
+// the two runtime booleans of a scan launch (a gate tensor z, row-index tables) as template arguments:
+// f(std::bool_constant<HAS_Z>, std::bool_constant<IDX>)
+template <typename A, typename F> static inline void with_z_idx(const A& a, F f) {
+    const bool idx = a.z_row_index != nullptr;   // validated: both tables or neither
+    if (a.z) {
+        if (idx) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (idx) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
 }
 template <typename A> static inline mix_args<A> mix_make(const A& a, const A* second, unsigned& gz) {
     mix_args<A> m;
@@ -305,18 +318,23 @@ __device__ __forceinline__ float sigmoid_f(float x) {
 }
 __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
 
-// Sum over the 64 lanes of a wave on the VALU's DPP path (every lane gets the total): 4 in-row butterfly steps, two
-// row broadcasts and one readlane, instead of 6 ds_bpermute round trips through the LDS pipe (__shfl_xor).
-__device__ __forceinline__ float wave_sum_dpp(float x) {
 #define DM_DPP_ADD(CTRL, ROWMASK) x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, ROWMASK, 0xF, true))
+// Sum over the 16 lanes of a DPP row (every lane of the row gets the total): 4 in-row butterfly steps.
+__device__ __forceinline__ float row_sum_dpp(float x) {
     DM_DPP_ADD(0xB1, 0xF);        // quad_perm [1,0,3,2]   : lane ^ 1
     DM_DPP_ADD(0x4E, 0xF);        // quad_perm [2,3,0,1]   : lane ^ 2
     DM_DPP_ADD(0x141, 0xF);       // row_half_mirror       : the other quad of the 8
     DM_DPP_ADD(0x140, 0xF);       // row_mirror            : the other half of the 16-lane row -> every lane = row total
+    return x;
+}
+// Sum over the 64 lanes of a wave on the VALU's DPP path (every lane gets the total): the row sum, two
+// row broadcasts and one readlane, instead of 6 ds_bpermute round trips through the LDS pipe (__shfl_xor).
+__device__ __forceinline__ float wave_sum_dpp(float x) {
+    x = row_sum_dpp(x);
     DM_DPP_ADD(0x142, 0xA);       // row_bcast15 into rows 1, 3 : += total of the row below
     DM_DPP_ADD(0x143, 0xC);       // row_bcast31 into rows 2, 3 : += total of rows 0..1
-#undef DM_DPP_ADD
     return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), 63));
 }
+#undef DM_DPP_ADD
 
 }  // namespace dm

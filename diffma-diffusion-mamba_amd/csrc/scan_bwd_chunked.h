@@ -22,18 +22,7 @@
 
 namespace dm {
 
-// sum over the 16 lanes of a DPP row (every lane of the row gets the total)
-__device__ __forceinline__ float row_sum16(float x) {
-#define DM_ROW_ADD(CTRL) x += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xF, 0xF, true))
-    DM_ROW_ADD(0xB1);         // quad_perm [1,0,3,2]
-    DM_ROW_ADD(0x4E);         // quad_perm [2,3,0,1]
-    DM_ROW_ADD(0x141);        // row_half_mirror
-    DM_ROW_ADD(0x140);        // row_mirror
-#undef DM_ROW_ADD
-    return x;
-}
-
-template <typename T, typename TBC, bool HAS_Z, bool IDX, int DMODE, int NW, int LC, bool ASH = false>   // DMODE: scan_bwd_impl.h
+template <typename T, typename TBC, bool HAS_Z, bool IDX, int DMODE, int NW, int LC, bool ASH = false>   // DMODE, ASH: scan_bwd_step.h
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) void scan_bwd_chunked_kernel(const mix_args<dm_scan_bwd_args> pm) {
     const dm_scan_bwd_args& p = pm.a[blockIdx.z];      // grid.z = congruent launches sharing this one (the two mixers of a block)
     constexpr int N = 16, NPL = N / 2, SUB = DM_SCAN_CKPT_EVERY, M = 2 * N;
@@ -111,10 +100,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
     auto finish_sub = [&](int sc, Sub& in) {                                      // softplus, zero gradients past the end
 #pragma unroll
         for (int i = 0; i < SUB; ++i) {
-            float x = in.dl[i];
-            if (DMODE != 2) x += bias;
-            if (DMODE == 1) x = softplus_f(x);
-            in.dl[i] = x;
+            in.dl[i] = activate_delta<DMODE>(in.dl[i], bias);
             in.gg[i] = ((l0 + sc * SUB + i) < L && active) ? in.gg[i] : 0.f;
         }
     };
@@ -135,24 +121,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
             const float dlo = valid ? in.dl[i] : 0.f;                              // steps past the end: decay 1, no contribution
             sd += dlo;
             float gy = in.gg[i];
-            if (HAS_Z) gy *= in.zz[i] * sigmoid_f(in.zz[i]);
+            if (HAS_Z) gy *= silu_f(in.zz[i]);
             const float* crow = &bc_lds[c][sc * SUB + i][N];
-            float a_sh = 0.f;
-            if (ASH) a_sh = fast_exp2(A2[0].x * dlo);
+            const float a_sh = decay_shared<ASH>(A2[0], dlo);
 #pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                f32x2 a, cc;
-                if (ASH) {
-                    a = (f32x2){a_sh, a_sh};
-                } else {
-                    const f32x2 t = A2[k] * dlo;
-                    a.x = fast_exp2(t.x);
-                    a.y = fast_exp2(t.y);
-                }
-                cc.x = crow[2 * k];
-                cc.y = crow[2 * k + 1];
-                carry[k] = a * (cc * gy + carry[k]);
-            }
+            for (int k = 0; k < NPL; ++k) carry_only_pair(carry[k], decay_pair<ASH>(A2[k], dlo, a_sh), (f32x2){crow[2 * k], crow[2 * k + 1]}, gy);
         }
     }
 #pragma unroll
@@ -189,7 +162,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
     if (MFMA_RED) mfma_selectors(lane, sel_lo, sel_hi);
 
     auto load_state = [&](int ci, uint32_t(&w)[H0W]) {                            // ci = global sub-chunk index (K2's convention)
-        const int slot = (ci > 0 && ci * SUB < L) ? ci : ((ci > 0 && ci * SUB == L) ? 0 : -1);
+        const int slot = ckpt_slot(ci, L);
         if (slot < 0) {
 #pragma unroll
             for (int k = 0; k < H0W; ++k) w[k] = 0u;
@@ -208,19 +181,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
             }
         }
     };
-    auto unpack_state = [&](f32x2(&h)[NPL], const uint32_t(&w)[H0W]) {
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            if constexpr (CK_PACKED) {
-                h[k].x = __uint_as_float(w[k] << 16);
-                h[k].y = __uint_as_float(w[k] & 0xffff0000u);
-            } else {
-                h[k].x = __uint_as_float(w[2 * k]);
-                h[k].y = __uint_as_float(w[2 * k + 1]);
-            }
-        }
-    };
-
     for (int sc = nsub - 1; sc >= 0; --sc) {
         const int ci = l0 / SUB + sc;
         Sub in;
@@ -230,7 +190,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
         load_state(ci + 1, w1);                                                   // state after its last step (= the next checkpoint, or slot 0)
         finish_sub(sc, in);
         f32x2 h[NPL], hs[SUB][NPL];
-        unpack_state(h, w0);
+        unpack_ckpt<CK_PACKED>(h, w0, 0);
 #pragma unroll
         for (int i = 0; i < SUB; ++i) {                                           // recompute: hs[i] = state before step sc*SUB + i
 #pragma unroll
@@ -239,25 +199,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
                 const float* brow = &bc_lds[c][sc * SUB + i][0];
                 const float dlo = in.dl[i];
                 const float du = dlo * in.uu[i];
-                float a_sh = 0.f;
-                if (ASH) a_sh = fast_exp2(A2[0].x * dlo);
+                const float a_sh = decay_shared<ASH>(A2[0], dlo);
 #pragma unroll
-                for (int k = 0; k < NPL; ++k) {
-                    f32x2 a, bb;
-                    if (ASH) {
-                        a = (f32x2){a_sh, a_sh};
-                    } else {
-                        const f32x2 t = A2[k] * dlo;
-                        a.x = fast_exp2(t.x);
-                        a.y = fast_exp2(t.y);
-                    }
-                    bb.x = brow[2 * k];
-                    bb.y = brow[2 * k + 1];
-                    h[k] = a * h[k] + bb * du;
-                }
+                for (int k = 0; k < NPL; ++k) recompute_pair(h[k], decay_pair<ASH>(A2[k], dlo, a_sh), (f32x2){brow[2 * k], brow[2 * k + 1]}, du);
             }
         }
-        unpack_state(h, w1);
+        unpack_ckpt<CK_PACKED>(h, w1, 0);
         // a partial last sub-chunk (L not a multiple of SUB): the state after its last VALID step is slot 0; the steps past the
         // end are exact no-ops (g = 0), and the states "before" them are never multiplied with a non-zero gradient
 #pragma unroll
@@ -267,65 +214,39 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
             const int l = valid ? lraw : L - 1;
             const float* brow = &bc_lds[c][sc * SUB + i][0];
             const float g = in.gg[i];
-            float sz = 1.f, gy = g;
-            if (HAS_Z) {
-                sz = sigmoid_f(in.zz[i]);
-                gy = g * in.zz[i] * sz;
-            }
+            float sz;
+            const float gy = gate_gy<HAS_Z>(g, in.zz[i], sz);
             const float dlo = in.dl[i];
             const float du = dlo * in.uu[i];
-            float a_rev = 0.f;
-            if (ASH) a_rev = fast_exp2(A2[0].x * dlo);
+            const float a_rev = decay_shared<ASH>(A2[0], dlo);
             f32x2 yp2 = (f32x2){0.f, 0.f}, GB2 = (f32x2){0.f, 0.f}, dlA2 = (f32x2){0.f, 0.f};
             float red[M];
             uint32_t pk_all[M / 2];
 #pragma unroll
             for (int k = 0; k < NPL; ++k) {
-                f32x2 bb, cc, a;
-                bb.x = brow[2 * k]; bb.y = brow[2 * k + 1];
-                cc.x = brow[N + 2 * k]; cc.y = brow[N + 2 * k + 1];
-                if (ASH) {
-                    a = (f32x2){a_rev, a_rev};
-                } else {
-                    const f32x2 t = A2[k] * dlo;
-                    a.x = fast_exp2(t.x);
-                    a.y = fast_exp2(t.y);
-                }
-                const f32x2 hj = h[k];
-                const f32x2 hp = hs[i][k];
-                yp2 += cc * hj;
-                const f32x2 G = cc * gy + carry[k];
-                const f32x2 dCp = hj * gy;
-                carry[k] = a * G;                                                 // (steps past the end: g = 0 and carry = 0, exact no-ops)
-                const f32x2 Gt = carry[k] * hp;
-                dlA2 += A2[k] * Gt;
-                dA[k] += Gt * dlo;
-                GB2 += G * bb;
-                const f32x2 dBp = G * du;
+                const f32x2 bb = {brow[2 * k], brow[2 * k + 1]}, cc = {brow[N + 2 * k], brow[N + 2 * k + 1]};
+                const f32x2 a = decay_pair<ASH>(A2[k], dlo, a_rev);
+                f32x2 dBp, dCp;                                                   // (steps past the end: g = 0 and carry = 0, exact no-ops)
+                adjoint_pair<HAS_Z, false>(h[k], hs[i][k], carry[k], dA[k], yp2, GB2, dlA2, A2[k], a, bb, cc, gy, du, dlo, dBp, dCp);
                 if constexpr (MFMA_RED) {
-                    pk_all[k] = pack_bf16(dBp.x, dBp.y);
-                    pk_all[NPL + k] = pack_bf16(dCp.x, dCp.y);
+                    pk_all[k] = pack_bf16(dBp);
+                    pk_all[NPL + k] = pack_bf16(dCp);
                 } else {
                     red[2 * k] = dBp.x;
                     red[2 * k + 1] = dBp.y;
                     red[N + 2 * k] = dCp.x;
                     red[N + 2 * k + 1] = dCp.y;
                 }
-                h[k] = hp;
             }
-            const float ypre = yp2.x + yp2.y + Dv * in.uu[i];
-            const float GB = GB2.x + GB2.y;
-            const float dlA = dlA2.x + dlA2.y;
-            float ddl = in.uu[i] * GB + LN2 * dlA;
-            const float duv = dlo * GB + gy * Dv;
-            if (DMODE != 0) ddl *= (1.0f - fast_exp2(-dlo * LOG2E));
-            dD_acc += gy * in.uu[i];
+            float ddl, duv, ypre, dDi;
+            step_outputs<DMODE, 1>(yp2, GB2, dlA2, in.uu[i], dlo, gy, Dv, ddl, duv, ypre, dDi);
+            dD_acc += dDi;
             dbias_acc += ddl;
             if (valid && active) {
                 bio<T>::st(r_du, vo, l * sl_du, duv);
                 bio<T>::st(r_ddt, vo, l * sl_ddt, ddl);
                 if (HAS_Z) {
-                    const float dzv = g * ypre * sz * (1.0f + in.zz[i] * (1.0f - sz));
+                    const float dzv = gate_grad(g, ypre, in.zz[i], sz);
                     bio<T>::st(r_dz, vo, in.zrow[i] * sl_dz, dzv);
                 }
             }
@@ -334,18 +255,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
             if constexpr (MFMA_RED) {
 #pragma unroll
                 for (int g16 = 0; g16 < M / 16; ++g16) {                          // g16 = 0: dB, 1: dC;  register r of lane l = value 4*(l>>4) + r
-                    const u32x4_t lo = {pk_all[8 * g16], pk_all[8 * g16 + 1], pk_all[8 * g16 + 2], pk_all[8 * g16 + 3]};
-                    const u32x4_t hi = {pk_all[8 * g16 + 4], pk_all[8 * g16 + 5], pk_all[8 * g16 + 6], pk_all[8 * g16 + 7]};
-                    f32x4 dsum = mfma_group_sum16(sel_lo, sel_hi, lo, hi);
+                    f32x4 dsum = group_sum16(sel_lo, sel_hi, pk_all + 8 * g16);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dsum[r] = row_sum16(dsum[r]);
+                    for (int r = 0; r < 4; ++r) dsum[r] = row_sum_dpp(dsum[r]);
                     if (valid && (lane & 15) == 0) *reinterpret_cast<f32x4*>(prow + g16 * N + 4 * (lane >> 4)) = dsum;
                 }
             } else {
                 lane_group_reduce<M>(red);                                        // register i = value 4*i + 2*b4 + b5
 #pragma unroll
                 for (int i8 = 0; i8 < M / 4; ++i8) {
-                    const float tot = row_sum16(red[i8]);
+                    const float tot = row_sum_dpp(red[i8]);
                     if (valid && (lane & 15) == 0) prow[4 * i8 + 2 * ((lane >> 4) & 1) + (lane >> 5)] = tot;
                 }
             }
@@ -399,39 +318,17 @@ static void launch_bwd_chunked3(const dm_scan_bwd_args& a, const dm_scan_bwd_arg
     unsigned gz;
     const mix_args<dm_scan_bwd_args> m = mix_make(a, second, gz);
     dim3 grid((a.dim + WAVE - 1) / WAVE, a.nseq, gz), block(WAVE * BWD_CHUNKED_NW);
-    const bool sp = (a.flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
-    if constexpr (HAS_Z && IDX) {
-        if ((a.flags & DM_FLAG_A_SHARED) && sp) {
-            hipLaunchKernelGGL((scan_bwd_chunked_kernel<T, TBC, true, true, 1, BWD_CHUNKED_NW, LC, true>), grid, block, 0, st, m);
-            return;
-        }
-    }
-    if constexpr (!HAS_Z && IDX) {                    // hoisted gate + hoisted softplus (the DiffMa mixer's call pattern)
-        if (a.flags & DM_FLAG_DELTA_ACTIVATED) {
-            hipLaunchKernelGGL((scan_bwd_chunked_kernel<T, TBC, false, true, 2, BWD_CHUNKED_NW, LC>), grid, block, 0, st, m);
-            return;
-        }
-    }
-    if (sp) hipLaunchKernelGGL((scan_bwd_chunked_kernel<T, TBC, HAS_Z, IDX, 1, BWD_CHUNKED_NW, LC>), grid, block, 0, st, m);
-    else hipLaunchKernelGGL((scan_bwd_chunked_kernel<T, TBC, HAS_Z, IDX, 0, BWD_CHUNKED_NW, LC>), grid, block, 0, st, m);
+    with_bwd_variant<16, HAS_Z, IDX>(a.flags, [&](auto dmode, auto ash) {
+        hipLaunchKernelGGL((scan_bwd_chunked_kernel<T, TBC, HAS_Z, IDX, dmode.value, BWD_CHUNKED_NW, LC, ash.value>), grid, block, 0, st, m);
+    });
 }
 
 template <typename T, typename TBC>
 static int launch_bwd_chunked(const dm_scan_bwd_args& a, const dm_scan_bwd_args* second, hipStream_t st, int lc) {
-    const bool idx = a.z_row_index != nullptr;
-#define DM_BWDC(HZ, IX)                                                                       \
-    do {                                                                                      \
-        if (lc == BWD_CHUNKED_LC_LONG) launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_LONG>(a, second, st); \
-        else launch_bwd_chunked3<T, TBC, HZ, IX, BWD_CHUNKED_LC_SHORT>(a, second, st);          \
-    } while (0)
-    if (a.z) {
-        if (idx) DM_BWDC(true, true);
-        else DM_BWDC(true, false);
-    } else {
-        if (idx) DM_BWDC(false, true);
-        else DM_BWDC(false, false);
-    }
-#undef DM_BWDC
+    with_z_idx(a, [&](auto hz, auto ix) {
+        if (lc == BWD_CHUNKED_LC_LONG) launch_bwd_chunked3<T, TBC, hz.value, ix.value, BWD_CHUNKED_LC_LONG>(a, second, st);
+        else launch_bwd_chunked3<T, TBC, hz.value, ix.value, BWD_CHUNKED_LC_SHORT>(a, second, st);
+    });
     return launch_status("dm_selective_scan_bwd (chunked)");
 }
 

@@ -33,7 +33,7 @@
 // with ~50 operations in flight a prefetched value was then waited for with vmcnt(19) right after 20 newer loads had been
 // issued -- i.e. for a load that had just left.  (profiles/r03_k2_experiments.txt #9.)
 #include <type_traits>
-#include "dm_common.h"
+#include "scan_bwd_step.h"   // the recurrence itself, shared with the chunk-parallel kernel (scan_bwd_chunked.h)
 
 namespace dm {
 
@@ -52,22 +52,6 @@ __device__ __forceinline__ void swap16(float& a, float& b) {   // odd 16-lane ro
     a = __uint_as_float(r[0]);
     b = __uint_as_float(r[1]);
 }
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xF, 0xF, true));
-}
-constexpr int DPP_QUAD_SWAP = 0xB1;     // [1,0,3,2]  lane ^ 1
-constexpr int DPP_QUAD_HALF = 0x4E;     // [2,3,0,1]  lane ^ 2
-constexpr int DPP_ROW_ROR = 0x120;      // + n : rotate right by n inside a 16-lane row
-
-// sum over the SPLIT consecutive lanes that share a channel (every lane gets the total)
-template <int SPLIT>
-__device__ __forceinline__ float slice_sum(float x) {
-    if (SPLIT >= 2) x += dpp<DPP_QUAD_SWAP>(x);
-    if (SPLIT >= 4) x += dpp<DPP_QUAD_HALF>(x);
-    return x;
-}
-
 // v[0 .. M) per lane (M = 2*NS).  Reduce-scatter over the 4 lane groups (16-lane rows) of the wave: after the call
 // register i (< M/4) of a lane holds the lane-group total of value
 //     4*i + 2*b4 + b5      (b5, b4 = bits 5, 4 of the lane id)
@@ -79,38 +63,6 @@ __device__ __forceinline__ void lane_group_reduce(float (&v)[M]) {
     for (int i = 0; i < M / 2; ++i) { swap32(v[2 * i], v[2 * i + 1]); v[i] = v[2 * i] + v[2 * i + 1]; }
 #pragma unroll
     for (int i = 0; i < M / 4; ++i) { swap16(v[2 * i], v[2 * i + 1]); v[i] = v[2 * i] + v[2 * i + 1]; }
-}
-
-// ---- matrix-pipe variant of the first two stages (16-bit I/O only) --------------------------------------
-// v_mfma_f32_16x16x32_bf16 with a 0/1 selector as the A fragment sums the B fragment over the 4 lane groups:
-// lane l supplies B[k = (l>>4, e)][j = l&15] = value e of lane l, and A[i = l&15][k = (l>>4, e)] = (e == i) gives
-// D[i][j] = sum_g value_i(lane j + 16 g).  Two instructions (values 0..7, 8..15) leave register r of lane l
-// holding the lane-group total of value 4*(l>>4) + r for row position l&15 -- the same reduce-scatter as the
-// 12 permlane swaps + 12 adds of lane_group_reduce, on the otherwise idle matrix pipe.  The products are rounded to bf16
-// first (they are re-rounded to the 16-bit I/O dtype later anyway); fp32 I/O keeps the exact VALU path.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    return dm_cvt_pk_bf16(lo, hi);
-}
-__device__ __forceinline__ void mfma_selectors(int lane, u32x4_t& a_lo, u32x4_t& a_hi) {
-    const int i = lane & 15;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        a_lo[p] = ((i == 2 * p) ? 0x3F80u : 0u) | ((i == 2 * p + 1) ? 0x3F800000u : 0u);
-        a_hi[p] = ((i == 2 * p + 8) ? 0x3F80u : 0u) | ((i == 2 * p + 9) ? 0x3F800000u : 0u);
-    }
-}
-__device__ __forceinline__ f32x4 mfma_group_sum16(const u32x4_t& a_lo, const u32x4_t& a_hi, const u32x4_t& v_lo, const u32x4_t& v_hi) {
-    f32x4 d = {0.f, 0.f, 0.f, 0.f};
-    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a_lo), __builtin_bit_cast(bf16x8_t, v_lo), d, 0, 0, 0);
-    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a_hi), __builtin_bit_cast(bf16x8_t, v_hi), d, 0, 0, 0);
-    return d;
-}
-// make a value opaque to the optimiser (costs no instruction): stops it from keeping the exp() / B-row
-// values of the recompute pass alive across the whole chunk just to save recomputing them
-__device__ __forceinline__ float opaque(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
 }
 
 // LDS rows of the staged B / C values are RE-READ at every use instead of being kept in VGPRs across the chunk: the chunk's base
@@ -138,9 +90,7 @@ __device__ __forceinline__ void lds_ld_vec(float (&v)[NS], lds_cfptr row) {
     }
 }
 
-// DMODE (delta mode): 0 = delta + bias used as is, 1 = softplus(delta + bias) (DM_FLAG_DELTA_SOFTPLUS), 2 = delta already holds
-// softplus(raw + bias) (DM_FLAG_DELTA_ACTIVATED: the producer of delta applied it once per element instead of every scan
-// direction twice); the returned ddelta is the gradient of the RAW value in every mode: softplus'(x) = 1 - exp(-softplus(x)).
+// DMODE (delta mode), ASH: scan_bwd_step.h
 template <typename T, typename TBC, int N, int SPLIT, bool HAS_Z, bool IDX, int DMODE, bool ASH = false>
 __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(N <= 16 ? 2 : 1))) void scan_bwd_kernel(const dm_scan_bwd_args p) {
     constexpr int NS = N / SPLIT, NPL = NS / 2, CW = WAVE / SPLIT, CK = BWD_CK, SUB = DM_SCAN_CKPT_EVERY, M = 2 * NS, R = M / 4;
@@ -267,8 +217,8 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float v = acc4[i];
-                v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-                v += __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(v), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
+                v += dpp<DPP_QUAD_SWAP>(v);
+                v += dpp<DPP_QUAD_HALF>(v);
                 acc4[i] = v;
             }
             const float mine = tq == 0 ? acc4[0] : (tq == 1 ? acc4[1] : (tq == 2 ? acc4[2] : acc4[3]));             // value 4 g4 + tq of step j
@@ -312,7 +262,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
     // (= the state after the last step) for 4 ci == L, zero for ci == 0 and past the end.
     constexpr int H0W = CK_PACKED ? NPL : 2 * NPL;               // 32-bit words per state slice
     auto load_state = [&](int ci, uint32_t(&w)[H0W]) {
-        const int slot_ = (ci > 0 && ci * SUB < L) ? ci : ((ci > 0 && ci * SUB == L) ? 0 : -1);      // wave-uniform
+        const int slot_ = ckpt_slot(ci, L);                                                          // wave-uniform
         const int vo_ = (slot_ < 0 || !p.ckpt) ? BIO_OOB : vo_ck;                                    // no slot: the loads return 0 (no branch)
         const int slot = slot_ < 0 ? 0 : slot_;
         if constexpr (CK_PACKED) {
@@ -326,17 +276,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
         }
     };
     auto unpack_state = [&](f32x2(&h)[NPH], const uint32_t(&w)[H0W], int hf) {       // group hf of the slice: pairs hf*NPH ..
-#pragma unroll
-        for (int k = 0; k < NPH; ++k) {
-            const int kk = hf * NPH + k;
-            if constexpr (CK_PACKED) {
-                h[k].x = __uint_as_float(w[kk] << 16);
-                h[k].y = __uint_as_float(w[kk] & 0xffff0000u);
-            } else {
-                h[k].x = __uint_as_float(w[2 * kk]);
-                h[k].y = __uint_as_float(w[2 * kk + 1]);
-            }
-        }
+        unpack_ckpt<CK_PACKED>(h, w, hf * NPH);
     };
     // ---- the software pipeline (round 3) ---------------------------------------------------------------------------------
     // Sub-chunks (SUB steps, one checkpoint) are processed last to first.  While sub-chunk ci is being recomputed and swept, the
@@ -414,10 +354,7 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
             for (int i = 0; i < SUB; ++i) {
                 const bool valid = (l0 + sc * SUB + i) < L;
                 uu[i] = bio<T>::cv(ru[i]);
-                float x = bio<T>::cv(rd[i]);
-                if (DMODE != 2) x += bias;
-                if (DMODE == 1) x = softplus_f(x);
-                dl[i] = x;                                    // tail steps re-read row L-1: finite garbage that only meets g = 0
+                dl[i] = activate_delta<DMODE>(bio<T>::cv(rd[i]), bias);   // tail steps re-read row L-1: finite garbage that only meets g = 0
                 zz[i] = HAS_Z ? bio<T>::cv(rz[i]) : 0.f;
                 gg[i] = (valid && active) ? bio<T>::cv(rg[i]) : 0.f;
             }
@@ -443,23 +380,12 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                 lds_ld_vec<2 * NPH>(Bv, brow);
                 const float dlo = CACHE_A ? dl[i] : opaque(dl[i]);
                 const float du = dlo * uu[i];
-                float a_sh = 0.f;
-                if (ASH) a_sh = fast_exp2(A2[0].x * dlo);             // DM_FLAG_A_SHARED: one decay factor for all states of the channel
+                const float a_sh = decay_shared<ASH>(A2[0], dlo);
 #pragma unroll
                 for (int k = 0; k < NPH; ++k) {
-                    f32x2 a;
-                    if (ASH) {
-                        a = (f32x2){a_sh, a_sh};
-                    } else {
-                        const f32x2 t = A2[hf * NPH + k] * dlo;
-                        a.x = fast_exp2(t.x);
-                        a.y = fast_exp2(t.y);
-                    }
+                    const f32x2 a = decay_pair<ASH>(A2[hf * NPH + k], dlo, a_sh);
                     if (CACHE_A) keep[k] = a;
-                    f32x2 bb;
-                    bb.x = Bv[2 * k];
-                    bb.y = Bv[2 * k + 1];
-                    h[k] = a * h[k] + bb * du;
+                    recompute_pair(h[k], a, (f32x2){Bv[2 * k], Bv[2 * k + 1]}, du);
                 }
             };
             f32x2 h[NPH];
@@ -511,15 +437,11 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
                     lds_ld_vec<2 * NPH>(Cv, brow + N);
                 }
                 const float g = gg[i];
-                float sz = 1.f, gy = g;
-                if (HAS_Z) {
-                    sz = sigmoid_f(zz[i]);
-                    gy = g * zz[i] * sz;
-                }
+                float sz;
+                const float gy = gate_gy<HAS_Z>(g, zz[i], sz);
                 const float dlo = (CACHE_A && i < SUB - 1) ? dl[i] : opaque(dl[i]);
                 const float du = dlo * uu[i];
-                float a_rev = 0.f;
-                if (ASH) a_rev = fast_exp2(A2[0].x * dlo);
+                const float a_rev = decay_shared<ASH>(A2[0], dlo);
                 f32x2 yp2 = (f32x2){0.f, 0.f}, GB2 = (f32x2){0.f, 0.f}, dlA2 = (f32x2){0.f, 0.f};
                 if (hf > 0) { GB2 = GB2s[i]; dlA2 = dlA2s[i]; if (HAS_Z) yp2 = yp2s[i]; }
                 float red[NH == 1 ? M : 1];
@@ -527,77 +449,43 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                 for (int k = 0; k < NPH; ++k) {
                     const int kk = hf * NPH + k;               // the pair's place among the lane's NPL pairs
-                    f32x2 bb, cc;
-                    bb.x = Bv[2 * k]; bb.y = Bv[2 * k + 1];
-                    cc.x = Cv[2 * k]; cc.y = Cv[2 * k + 1];
-                    f32x2 a;
-                    if (ASH) {
-                        a = (f32x2){a_rev, a_rev};
-                    } else if (CACHE_A && i < SUB - 1) {
-                        a = aa[CACHE_A ? i : 0][k];
-                    } else {
-                        const f32x2 t = A2[kk] * dlo;
-                        a.x = fast_exp2(t.x);
-                        a.y = fast_exp2(t.y);
-                    }
-                    const f32x2 hj = h[k];
-                    const f32x2 hp = hs[i][k];
-                    if (HAS_Z) yp2 += cc * hj;
-                    const f32x2 G = cc * gy + carry[kk];         // dL/dh_j
-                    const f32x2 dCp = hj * gy;
-                    carry[kk] = a * G;                           // a_j * dL/dh_j, flows to step j-1
-                    const f32x2 Gt = carry[kk] * hp;             // = G * a * h_{j-1}
-                    dlA2 += A2[kk] * Gt;
-                    dA[kk] += Gt * dlo;
-                    dA[kk].x = opaque(dA[kk].x);                 // accumulate NOW: left alone the scheduler defers all 8 steps'
-                    dA[kk].y = opaque(dA[kk].y);                 // products to the chunk end and keeps 64 VGPRs alive for them
-                    GB2 += G * bb;
-                    const f32x2 dBp = G * du;
+                    const f32x2 bb = {Bv[2 * k], Bv[2 * k + 1]}, cc = {Cv[2 * k], Cv[2 * k + 1]};
+                    // the sweep reuses the decay factors the recompute kept (CACHE_A), else evaluates them again
+                    const f32x2 a = (CACHE_A && i < SUB - 1) ? aa[CACHE_A ? i : 0][k] : decay_pair<ASH>(A2[kk], dlo, a_rev);
+                    f32x2 dBp, dCp;
+                    adjoint_pair<HAS_Z, true>(h[k], hs[i][k], carry[kk], dA[kk], yp2, GB2, dlA2, A2[kk], a, bb, cc, gy, du, dlo, dBp, dCp);
                     if constexpr (MFMA_RED) {
-                        pk_all[k] = pack_bf16(dBp.x, dBp.y);
-                        pk_all[NPH + k] = pack_bf16(dCp.x, dCp.y);
+                        pk_all[k] = pack_bf16(dBp);
+                        pk_all[NPH + k] = pack_bf16(dCp);
                     } else {
                         red[2 * k] = dBp.x;
                         red[2 * k + 1] = dBp.y;
                         red[NS + 2 * k] = dCp.x;
                         red[NS + 2 * k + 1] = dCp.y;
                     }
-                    h[k] = hp;
                 }
                 if (hf < NH - 1) { GB2s[i] = GB2; dlA2s[i] = dlA2; if (HAS_Z) yp2s[i] = yp2; }
                 if (hf == NH - 1) {
-                const float ypre = slice_sum<SPLIT>(yp2.x + yp2.y) + Dv * uu[i];
-                const float GB = slice_sum<SPLIT>(GB2.x + GB2.y);
-                const float dlA = slice_sum<SPLIT>(dlA2.x + dlA2.y);
-                float ddl = uu[i] * GB + LN2 * dlA;
-                const float duv = dlo * GB + gy * Dv;
-                if (DMODE != 0) ddl *= (1.0f - fast_exp2(-dlo * LOG2E));   // softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x))
+                float ddl, duv, ypre, dDi;
+                step_outputs<DMODE, SPLIT>(yp2, GB2, dlA2, uu[i], dlo, gy, Dv, ddl, duv, ypre, dDi);
                 if (q == 0) {                                             // one lane per channel owns the channel sums
-                    dD_acc += gy * uu[i];
+                    dD_acc += dDi;
                     dbias_acc += ddl;
                 }
                 const int vo_s = valid ? vo_st : BIO_OOB;
                 bio<T>::st_cv(r_du, vo_s, l * sl_du, duv);
                 bio<T>::st_cv(r_ddt, vo_s, l * sl_ddt, ddl);
                 if (HAS_Z) {
-                    const float dzv = g * ypre * sz * (1.0f + zz[i] * (1.0f - sz));
+                    const float dzv = gate_grad(g, ypre, zz[i], sz);
                     bio<T>::st_cv(r_dz, vo_s, zrow[i] * sl_dz, dzv);
                 }
                 }
-                if constexpr (MFMA_RED && NH == 2) {
-                    // this group's 16 values (dB and dC of its 8 states) = ONE pair of MFMAs; LDS group hf (flush_dbc maps the columns)
-                    const u32x4_t lo = {pk_all[0], pk_all[1], pk_all[2], pk_all[3]};
-                    const u32x4_t hi = {pk_all[4], pk_all[5], pk_all[6], pk_all[7]};
-                    const f32x4 dsum = mfma_group_sum16(sel_lo, sel_hi, lo, hi);
-                    *reinterpret_cast<f32x4*>(&red_lds[wave][j][hf * RED_HALF + red_slot]) = dsum;
-                } else if constexpr (MFMA_RED) {
+                if constexpr (MFMA_RED) {
+                    // 16 values (8 pairs) per pair of MFMAs; register r of group g16 = value 16*g16 + 4*(lane>>4) + r.  HALVES: this group's
+                    // 16 values (dB and dC of its 8 states) are ONE pair, LDS group hf (flush_dbc maps the columns)
 #pragma unroll
-                    for (int g16 = 0; g16 < M / 16; ++g16) {   // 16 values (8 pairs) per pair of MFMAs; register r of group g16 = value 16*g16 + 4*(lane>>4) + r
-                        const u32x4_t lo = {pk_all[8 * g16], pk_all[8 * g16 + 1], pk_all[8 * g16 + 2], pk_all[8 * g16 + 3]};
-                        const u32x4_t hi = {pk_all[8 * g16 + 4], pk_all[8 * g16 + 5], pk_all[8 * g16 + 6], pk_all[8 * g16 + 7]};
-                        const f32x4 dsum = mfma_group_sum16(sel_lo, sel_hi, lo, hi);
-                        *reinterpret_cast<f32x4*>(&red_lds[wave][j][g16 * RED_HALF + red_slot]) = dsum;
-                    }
+                    for (int g16 = 0; g16 < M / 16 / NH; ++g16)
+                        *reinterpret_cast<f32x4*>(&red_lds[wave][j][(NH == 2 ? hf : g16) * RED_HALF + red_slot]) = group_sum16(sel_lo, sel_hi, pk_all + 8 * g16);
                 } else {
                     lane_group_reduce<M>(red);
 #pragma unroll
@@ -634,38 +522,30 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 // profiles/r03_k2_experiments.txt), half of one at d_state 32
 template <int N> struct bwd_split { static constexpr int value = N >= 32 ? 2 : 1; };
 
-template <typename T, typename TBC, int N, bool HAS_Z, bool IDX>
-static void launch_bwd2(const dm_scan_bwd_args& a, hipStream_t st, dim3 grid) {
-    if constexpr (N == 16 && HAS_Z && IDX) {          // the one-exp variant is built for the Mamba-2 call pattern only
-        if ((a.flags & DM_FLAG_A_SHARED) && (a.flags & DM_FLAG_DELTA_SOFTPLUS)) {
-            hipLaunchKernelGGL((scan_bwd_kernel<T, TBC, N, bwd_split<N>::value, true, true, 1, true>), grid, dim3(WAVE * BWD_WAVES), 0, st, a);
-            return;
-        }
+// The one rule for which (DMODE, ASH) instantiation a launch takes, for K2 and K2c alike: calls
+// f(std::integral_constant<int, DMODE>, std::bool_constant<ASH>).  The special forms are built for their call pattern only.
+template <int N, bool HAS_Z, bool IDX, typename F>
+static void with_bwd_variant(int flags, F f) {
+    const bool sp = (flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
+    if constexpr (N == 16 && HAS_Z && IDX) {          // the one-exp variant: the Mamba-2 call pattern
+        if ((flags & DM_FLAG_A_SHARED) && sp) return f(std::integral_constant<int, 1>{}, std::true_type{});
     }
     if constexpr (N == 16 && !HAS_Z && IDX) {         // the hoisted-gate / hoisted-softplus call pattern of the DiffMa mixer
-        if (a.flags & DM_FLAG_DELTA_ACTIVATED) {
-            hipLaunchKernelGGL((scan_bwd_kernel<T, TBC, N, bwd_split<N>::value, false, true, 2>), grid, dim3(WAVE * BWD_WAVES), 0, st, a);
-            return;
-        }
+        if (flags & DM_FLAG_DELTA_ACTIVATED) return f(std::integral_constant<int, 2>{}, std::false_type{});
     }
-    if (a.flags & DM_FLAG_DELTA_SOFTPLUS)
-        hipLaunchKernelGGL((scan_bwd_kernel<T, TBC, N, bwd_split<N>::value, HAS_Z, IDX, 1>), grid, dim3(WAVE * BWD_WAVES), 0, st, a);
-    else
-        hipLaunchKernelGGL((scan_bwd_kernel<T, TBC, N, bwd_split<N>::value, HAS_Z, IDX, 0>), grid, dim3(WAVE * BWD_WAVES), 0, st, a);
+    if (sp) f(std::integral_constant<int, 1>{}, std::false_type{});
+    else f(std::integral_constant<int, 0>{}, std::false_type{});
 }
 
 template <typename T, typename TBC, int N>
 static int launch_bwd(const dm_scan_bwd_args& a, hipStream_t st) {
-    constexpr int WGCH = (WAVE / bwd_split<N>::value) * BWD_WAVES;   // channels per workgroup
+    constexpr int SPLIT = bwd_split<N>::value, WGCH = (WAVE / SPLIT) * BWD_WAVES;   // channels per workgroup
     dim3 grid((a.dim + WGCH - 1) / WGCH, a.nseq);
-    const bool idx = a.z_row_index != nullptr;
-    if (a.z) {
-        if (idx) launch_bwd2<T, TBC, N, true, true>(a, st, grid);
-        else launch_bwd2<T, TBC, N, true, false>(a, st, grid);
-    } else {
-        if (idx) launch_bwd2<T, TBC, N, false, true>(a, st, grid);
-        else launch_bwd2<T, TBC, N, false, false>(a, st, grid);
-    }
+    with_z_idx(a, [&](auto hz, auto ix) {
+        with_bwd_variant<N, hz.value, ix.value>(a.flags, [&](auto dmode, auto ash) {
+            hipLaunchKernelGGL((scan_bwd_kernel<T, TBC, N, SPLIT, hz.value, ix.value, dmode.value, ash.value>), grid, dim3(WAVE * BWD_WAVES), 0, st, a);
+        });
+    });
     return launch_status("dm_selective_scan_bwd");
 }
 

@@ -215,14 +215,7 @@ static void launch_fwd_chunked2(const dm_scan_fwd_args& a, const dm_scan_fwd_arg
 
 template <typename T, typename TBC>
 static int launch_fwd_chunked(const dm_scan_fwd_args& a, const dm_scan_fwd_args* second, hipStream_t st) {
-    const bool idx = a.z_row_index != nullptr;
-    if (a.z) {
-        if (idx) launch_fwd_chunked2<T, TBC, true, true>(a, second, st);
-        else launch_fwd_chunked2<T, TBC, true, false>(a, second, st);
-    } else {
-        if (idx) launch_fwd_chunked2<T, TBC, false, true>(a, second, st);
-        else launch_fwd_chunked2<T, TBC, false, false>(a, second, st);
-    }
+    with_z_idx(a, [&](auto hz, auto ix) { launch_fwd_chunked2<T, TBC, hz.value, ix.value>(a, second, st); });
     return launch_status("dm_selective_scan_fwd (chunked)");
 }
 

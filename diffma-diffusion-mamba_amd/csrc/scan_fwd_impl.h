@@ -298,14 +298,7 @@ static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st, dim3 grid) {
 template <typename T, typename TBC, int N>
 static int launch_fwd(const dm_scan_fwd_args& a, hipStream_t st) {
     dim3 grid((a.dim + WAVE - 1) / WAVE, a.nseq);
-    const bool idx = a.z_row_index != nullptr;   // validated: both tables or neither
-    if (a.z) {
-        if (idx) launch_fwd3<T, TBC, N, true, true>(a, st, grid);
-        else launch_fwd3<T, TBC, N, true, false>(a, st, grid);
-    } else {
-        if (idx) launch_fwd3<T, TBC, N, false, true>(a, st, grid);
-        else launch_fwd3<T, TBC, N, false, false>(a, st, grid);
-    }
+    with_z_idx(a, [&](auto hz, auto ix) { launch_fwd3<T, TBC, N, hz.value, ix.value>(a, st, grid); });
     return launch_status("dm_selective_scan_fwd");
 }
 

@@ -486,8 +486,9 @@ def _grads_to_cpu(*leaves):
 
 
 def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bsz=None, a_shared=False, dout_per_seq=False,
-                   variant="sequential", long_memory=False):
-    """a_shared: A[d, :] is one value per channel and the kernels run their DM_FLAG_A_SHARED form (one exp per channel-step, the
+                   variant="sequential", long_memory=False, delta_softplus=True, bc_fp32=False):
+    """delta_softplus=False: delta + bias is used as it is (the kernels' delta mode 0), so both are made positive here; bc_fp32: B / C
+    travel as fp32 tensors (holding the values rounded to dtype) next to 16-bit u / delta / z / dout.  a_shared: A[d, :] is one value per channel and the kernels run their DM_FLAG_A_SHARED form (one exp per channel-step, the
     Mamba-2 call pattern); dout_per_seq: the incoming gradient is per direction [S, L, Dm] in token order, read through
     out_row_index (DM_FLAG_DOUT_PER_SEQ) instead of one merged gradient per batch element."""
     from diffma_amd import hip_ops
@@ -500,17 +501,23 @@ def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bs
     if a_shared:
         host["A"] = host["A"][:, :1].expand(Dm, N).contiguous()
         d["A"] = host["A"].to(gpu)
+    if not delta_softplus:                 # a negative step would make the state grow: activate delta here, keep a small positive bias
+        host["delta"] = torch.nn.functional.softplus(host["delta"].float() + host["bias"]).to(dtype)
+        host["bias"] = host["bias"].abs() * 0.1
+        d["delta"], d["bias"] = host["delta"].to(gpu), host["bias"].to(gpu)
+    if bc_fp32:
+        d["B"], d["C"] = host["B"].float().to(gpu), host["C"].float().to(gpu)
     g = torch.Generator().manual_seed(seed + 1)
     K = hip_ops.SCAN_CKPT_EVERY
     ckpt = hip_ops.alloc_scan_ckpt(S, L, N, Dm, dtype, gpu).zero_()
     kw = {}
     if indexed:
         ndir = S // Bsz
-        zsrc = torch.randn(Bsz, L, Dm, generator=g).to(dtype)
+        zsrc = torch.randn(Bsz, L, Dm, generator=g).to(dtype) if with_z else None       # no gate: the tables still route dout / out
         zperm = torch.stack([torch.randperm(L, generator=g) for _ in range(ndir)]).int()
         operm = torch.stack([torch.randperm(L, generator=g) for _ in range(ndir)]).int()
         kw = dict(z_row_index=zperm.to(gpu), out_row_index=operm.to(gpu), batch_per_dir=Bsz)
-        zdev = zsrc.to(gpu)
+        zdev = None if zsrc is None else zsrc.to(gpu)
         # gradient of the MERGED output (token order), or one gradient per direction (token order as well)
         dout = torch.randn(S if dout_per_seq else Bsz, L, Dm, generator=g).to(dtype)
     else:
@@ -519,10 +526,10 @@ def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bs
     # variant: the kernel family under test (both the forward that writes the checkpoints and the backward); the library's own
     # choice by launch size would send every small test shape to the chunk-parallel kernels
     fwd_variant = variant if (variant != "chunked" or (16 * 14 // 4 < L <= 196 and N == 16)) else "sequential"
-    out = hip_ops.scan_fwd(d["u"], d["delta"], d["A"], d["B"], d["C"], d["D"], zdev, d["bias"], True,
+    out = hip_ops.scan_fwd(d["u"], d["delta"], d["A"], d["B"], d["C"], d["D"], zdev, d["bias"], delta_softplus,
                            ckpt=ckpt, ckpt_every=K, a_shared=a_shared, variant=fwd_variant, **kw)
     res = hip_ops.scan_bwd(d["u"], d["delta"], d["A"], d["B"], d["C"], d["D"], zdev, d["bias"], dout.to(gpu), ckpt,
-                           True, ckpt_every=K, a_shared=a_shared, dout_per_seq=dout_per_seq, variant=variant, **kw)
+                           delta_softplus, ckpt_every=K, a_shared=a_shared, dout_per_seq=dout_per_seq, variant=variant, **kw)
     torch.cuda.synchronize()
     du, ddelta, dz, dB, dC, dA, dD, dbias = [None if t is None else t.float().cpu().double() for t in res]
 
@@ -533,11 +540,12 @@ def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bs
     cm = lambda t: t.permute(0, 2, 1)
     dout_o = dout.float().double().to(odev)
     if indexed:
-        z = leaf(zsrc)
+        z = leaf(zsrc) if with_z else None
         ndir = S // Bsz
         zp_o, op_o = zperm.long().to(odev), operm.long().to(odev)
-        zs = torch.cat([z[:, zp_o[k], :] for k in range(ndir)], 0)        # [S, L, Dm] gathered
-        y = cm(selective_scan_ref(cm(u), cm(dl), A, cm(Bm), cm(Cm), Dp, z=cm(zs), delta_bias=bias, delta_softplus=True))
+        zs = None if z is None else torch.cat([z[:, zp_o[k], :] for k in range(ndir)], 0)        # [S, L, Dm] gathered
+        y = cm(selective_scan_ref(cm(u), cm(dl), A, cm(Bm), cm(Cm), Dp, z=None if zs is None else cm(zs), delta_bias=bias,
+                                  delta_softplus=delta_softplus))
         # scatter: merged[b, operm[k][l]] += y[k*Bsz+b, l]
         if dout_per_seq:                   # direction k's step l lands in row operm[k][l] of ITS OWN token-order slab
             loss = 0
@@ -552,7 +560,7 @@ def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bs
     else:
         z = leaf(host["z"]) if with_z else None
         y = cm(selective_scan_ref(cm(u), cm(dl), A, cm(Bm), cm(Cm), Dp, z=None if z is None else cm(z), delta_bias=bias,
-                                  delta_softplus=True))
+                                  delta_softplus=delta_softplus))
         loss = (y * dout_o).sum()
     loss.backward()
     u, dl, A, Bm, Cm, Dp, bias, z = _grads_to_cpu(u, dl, A, Bm, Cm, Dp, bias, z)
@@ -574,7 +582,7 @@ def _scan_bwd_case(gpu, dtype, S, L, Dm, N, seed, with_z=True, indexed=False, Bs
 
     chk(du, u.grad, "du")
     chk(ddelta, dl.grad, "ddelta")
-    if indexed:
+    if indexed and with_z:
         # dz slabs are per direction in token order: sum them
         chk(dz.view(S // Bsz, Bsz, L, Dm).sum(0), z.grad, "dz")
     elif with_z:
@@ -622,6 +630,18 @@ def test_scan_bwd_bench_instantiation(gpu, dtype, L):
     _scan_bwd_case(gpu, dtype, 6, L, 1024, 16, seed=100 + L, indexed=True, Bsz=2)
 
 
+# The K2c instantiations the rows below leave out, at the smallest shapes that cross chunks and leave ragged tails: 72 channels (one
+# full and one partial wave), L = 20 (8 steps per wave: three chunks, the last sub-chunk partial) and L = 60 (28 steps per wave:
+# three chunks).  Gate x row tables x delta mode 0 / 1 x the one-exp form, each at both chunk lengths.
+_K2C_GATE_IDX = [dict(), dict(with_z=False), dict(indexed=True, Bsz=1), dict(indexed=True, Bsz=1, with_z=False)]
+_K2C_REST = ([(2, 20, 72, dict(with_z=False)), (3, 20, 72, dict(indexed=True, Bsz=1, with_z=False)), (3, 60, 72, dict(indexed=True, Bsz=1, with_z=False)),
+              (3, 20, 72, dict(indexed=True, Bsz=1, a_shared=True, dout_per_seq=True))]
+             + [(3, L, 72, dict(delta_softplus=False, **kw)) for L in (20, 60) for kw in _K2C_GATE_IDX])
+# ... and all of them with fp32 B / C next to 16-bit I/O
+_K2C_FP32_BC = [(3, L, 72, dict(bc_fp32=True, delta_softplus=sp, **kw)) for L in (20, 60) for sp in (True, False) for kw in _K2C_GATE_IDX] + \
+               [(3, L, 72, dict(bc_fp32=True, indexed=True, Bsz=1, a_shared=True, dout_per_seq=True)) for L in (20, 60)]
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("S,L,Dm,kw", [
     (6, 196, 1024, dict(indexed=True, Bsz=2)),                    # the model's call at batch 2: 7 waves x 28 steps
@@ -631,10 +651,17 @@ def test_scan_bwd_bench_instantiation(gpu, dtype, L):
     (6, 49, 256, dict(indexed=True, Bsz=2)),                      # L = 49 (DiffMa-*/4): 7 waves x 8 steps
     (2, 30, 128, dict()),
     (3, 196, 256, dict(indexed=True, Bsz=1, a_shared=True, dout_per_seq=True)),   # the Mamba-2 call pattern
-])
+] + _K2C_REST)
 def test_scan_bwd_chunk_parallel_variant(gpu, dtype, S, L, Dm, kw):
     """K2c (csrc/scan_bwd_chunked.h): NW waves per (sequence, 64 channels), two passes joined by the linearity of the adjoint
     carry -- every gradient against fp64 autograd of the oracle, same tolerances as the sequential kernel."""
+    _scan_bwd_case(gpu, dtype, S, L, Dm, 16, seed=7 * L + Dm, variant="chunked", **kw)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("S,L,Dm,kw", _K2C_FP32_BC)
+def test_scan_bwd_chunk_parallel_fp32_bc(gpu, dtype, S, L, Dm, kw):
+    """K2c with fp32 B / C and 16-bit I/O: _scan_bwd_case, same checks and tolerances."""
     _scan_bwd_case(gpu, dtype, S, L, Dm, 16, seed=7 * L + Dm, variant="chunked", **kw)
 
 
@@ -1014,7 +1041,7 @@ def test_dtproj_softplus_matches_torch(gpu, dtype, M, Dm, R, P):
     torch.testing.assert_close(delta.cpu().double(), ref, rtol=rtol, atol=atol)
 
 
-def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed, long_memory=False):
+def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed, long_memory=False, bc_fp32=False):
     """The DiffMa mixer's call pattern after the hoists: no z, row-index tables, delta already activated (DM_FLAG_DELTA_ACTIVATED),
     the pre-gated gradient shared by the directions.  Forward and backward against fp64 autograd of the oracle run on the SAME
     activated delta; ddelta / dbias must be the gradients of the RAW pre-activation, i.e. times 1 - exp(-delta)."""
@@ -1023,6 +1050,8 @@ def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed, long_memory=
 
     N, S = 16, ndir * Bsz
     host, d = (_inputs_long_memory if long_memory else _inputs)(S, L, Dm, N, dtype, seed=seed, dev=gpu, with_z=False)
+    if bc_fp32:                            # fp32 B / C tensors (values rounded to dtype) next to 16-bit I/O
+        d["B"], d["C"] = host["B"].float().to(gpu), host["C"].float().to(gpu)
     g = torch.Generator().manual_seed(seed + 1)
     act = torch.nn.functional.softplus(host["delta"].float() + host["bias"]).to(dtype)      # what dm_dtproj_softplus_fwd would hand over
     perm = torch.stack([torch.randperm(L, generator=g) for _ in range(ndir)]).int()
@@ -1075,6 +1104,13 @@ def _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed, long_memory=
                                                    (2, 196, 128, 3, "chunked"), (1, 100, 200, 3, "chunked"), (2, 49, 128, 3, "chunked")])
 def test_scan_hoisted_call_pattern_matches_oracle_autograd(gpu, dtype, Bsz, L, Dm, ndir, variant):
     _hoisted_scan_case(gpu, dtype, Bsz, L, Dm, ndir, variant, seed=7 * L + Dm)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("L", [20, 60])
+def test_scan_hoisted_call_pattern_chunked_fp32_bc(gpu, dtype, L):
+    """K2c's activated-delta form with fp32 B / C and 16-bit I/O, at both chunk lengths (8 and 28 steps per wave)."""
+    _hoisted_scan_case(gpu, dtype, 1, L, 72, 3, "chunked", seed=7 * L + 72, bc_fp32=True)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
