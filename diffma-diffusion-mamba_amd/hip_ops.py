@@ -245,6 +245,34 @@ def _variant_flag(variant):
     return {"sequential": DM_FLAG_SCAN_SEQUENTIAL, "chunked": DM_FLAG_SCAN_CHUNKED}[variant]
 
 
+def _scan_args(a, u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, delta_activated, z_row_index, out_row_index, batch_per_dir,
+               ckpt, ckpt_every, ngroups, a_shared, variant, more_flags=0):
+    """The flag word and the fields that dm_scan_fwd_args and dm_scan_bwd_args share.  A, D, delta_bias: fp32 contiguous (_f32c), held
+    by the caller until it has launched."""
+    N = A.shape[1]
+    a.nseq, a.seqlen, a.dim, a.dstate = u.shape[0], u.shape[1], u.shape[2], N
+    a.ngroups = ngroups
+    a.batch_per_dir = batch_per_dir
+    a.io_dtype = dtype_code(u)
+    a.bc_dtype = dtype_code(Bm)
+    a.flags = (DM_FLAG_DELTA_SOFTPLUS if delta_softplus else 0) | (DM_FLAG_A_SHARED if a_shared else 0) | _variant_flag(variant) | more_flags
+    if delta_activated:
+        a.flags = (a.flags & ~DM_FLAG_DELTA_SOFTPLUS) | DM_FLAG_DELTA_ACTIVATED
+    a.ckpt_every = ckpt_every
+    a.ckpt_dtype = _ckpt_dtype_code(ckpt)
+    a.u, a.delta, a.z, a.ckpt = _ptr(u), _ptr(delta), _ptr(z), _ptr(ckpt)
+    a.B, a.C, a.A, a.D, a.delta_bias = _ptr(Bm), _ptr(Cm), _ptr(A), _ptr(D), _ptr(delta_bias)
+    a.z_row_index, a.out_row_index = _ptr(z_row_index), _ptr(out_row_index)
+    a.u_ss, a.u_sl, a.u_sd = u.stride()
+    a.dt_ss, a.dt_sl, a.dt_sd = delta.stride()
+    if z is not None:
+        a.z_ss, a.z_sl, a.z_sd = z.stride()
+    a.B_ss, a.B_sl, a.B_sn = Bm.stride()
+    a.C_ss, a.C_sl, a.C_sn = Cm.stride()
+    a.B_sg = a.C_sg = N
+    return a
+
+
 def scan_fwd(u, delta, A, Bm, Cm, D=None, z=None, delta_bias=None, delta_softplus=True, *,
              z_row_index=None, out_row_index=None, batch_per_dir=0, out=None, ckpt=None,
              ckpt_every=SCAN_CKPT_EVERY, last_state=None, ngroups=1, a_shared=False, variant=None, acc_dirs=False,
@@ -278,33 +306,11 @@ def _scan_fwd_launch(u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, z_ro
                      ckpt_every, last_state, ngroups, a_shared, variant, accumulate, delta_activated=False):
     S, L, Dm = u.shape
     N = A.shape[1]
-    A = _f32c(A)
-    D = _f32c(D)
-    delta_bias = _f32c(delta_bias)
-    a = dm_scan_fwd_args()
-    a.nseq, a.dim, a.seqlen, a.dstate = S, Dm, L, N
-    a.ngroups = ngroups
-    a.batch_per_dir = batch_per_dir
-    a.io_dtype = dtype_code(u)
-    a.bc_dtype = dtype_code(Bm)
-    a.flags = ((DM_FLAG_DELTA_SOFTPLUS if delta_softplus else 0) | (DM_FLAG_A_SHARED if a_shared else 0) | _variant_flag(variant)
-               | (DM_FLAG_OUT_ACCUMULATE if accumulate else 0))
-    if delta_activated:
-        a.flags = (a.flags & ~DM_FLAG_DELTA_SOFTPLUS) | DM_FLAG_DELTA_ACTIVATED
-    a.ckpt_every = ckpt_every
-    a.ckpt_dtype = _ckpt_dtype_code(ckpt)
-    a.u, a.delta, a.z, a.out = _ptr(u), _ptr(delta), _ptr(z), _ptr(out)
-    a.B, a.C, a.A, a.D, a.delta_bias = _ptr(Bm), _ptr(Cm), _ptr(A), _ptr(D), _ptr(delta_bias)
-    a.z_row_index, a.out_row_index = _ptr(z_row_index), _ptr(out_row_index)
-    a.ckpt, a.last_state = _ptr(ckpt), _ptr(last_state)
-    a.u_ss, a.u_sl, a.u_sd = u.stride()
-    a.dt_ss, a.dt_sl, a.dt_sd = delta.stride()
-    if z is not None:
-        a.z_ss, a.z_sl, a.z_sd = z.stride()
+    A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
+    a = _scan_args(dm_scan_fwd_args(), u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, delta_activated, z_row_index, out_row_index,
+                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, variant, DM_FLAG_OUT_ACCUMULATE if accumulate else 0)
+    a.out, a.last_state = _ptr(out), _ptr(last_state)
     a.o_ss, a.o_sl, a.o_sd = out.stride()
-    a.B_ss, a.B_sl, a.B_sn = Bm.stride()
-    a.C_ss, a.C_sl, a.C_sn = Cm.stride()
-    a.B_sg = a.C_sg = N
     nbytes = scan_fwd_algorithmic_bytes(S, Dm, L, N, u.element_size(), Bm.element_size(), z is not None)
     design = nbytes
     if accumulate:                               # the running sum is read back once per accumulating launch
@@ -326,16 +332,14 @@ def scan_bwd(u, delta, A, Bm, Cm, D, z, delta_bias, dout, ckpt, delta_softplus=T
     _require_gpu(u, delta, A, Bm, Cm, z, dout, ckpt)
     S, L, Dm = u.shape
     N = A.shape[1]
-    flags = ((DM_FLAG_DELTA_SOFTPLUS if delta_softplus else 0) | (DM_FLAG_DOUT_PER_SEQ if dout_per_seq else 0)
-             | (DM_FLAG_A_SHARED if a_shared else 0) | _variant_flag(variant))
-    if delta_activated:
-        flags = (flags & ~DM_FLAG_DELTA_SOFTPLUS) | DM_FLAG_DELTA_ACTIVATED
-    gc = _lib.load().dm_scan_bwd_launch_group_channels(S, Dm, L, N, flags)   # 256 (sequential kernel) or 64 (chunk-parallel, small launches)
+    A32, D32, b32 = _f32c(A), _f32c(D), _f32c(delta_bias)
+    a = _scan_args(dm_scan_bwd_args(), u, delta, A32, Bm, Cm, D32, z, b32, delta_softplus, delta_activated, z_row_index, out_row_index,
+                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, variant, DM_FLAG_DOUT_PER_SEQ if dout_per_seq else 0)
+    gc = _lib.load().dm_scan_bwd_launch_group_channels(S, Dm, L, N, a.flags)   # 256 (sequential kernel) or 64 (chunk-parallel, small launches)
     if gc <= 0:
         raise _lib.DiffmaHipError(f"selective-scan backward is not built for d_state={N}")
     nw = (Dm + gc - 1) // gc
     dev = u.device
-    A32, D32, b32 = _f32c(A), _f32c(D), _f32c(delta_bias)
     du = du_out if du_out is not None else torch.empty_like(u)      # du_out: a [S, L, Dm] view with channel stride 1
     ddelta = torch.empty((S, L, Dm), dtype=u.dtype, device=dev)
     dz = None
@@ -349,32 +353,14 @@ def scan_bwd(u, delta, A, Bm, Cm, D, z, delta_bias, dout, ckpt, delta_softplus=T
     dA = part[:, :Dm * N]
     dD = part[:, Dm * N:Dm * N + Dm] if want_dD else None
     dbias = part[:, pcols - Dm:] if want_db else None
-    a = dm_scan_bwd_args()
     a.part_ss = pcols
-    a.nseq, a.dim, a.seqlen, a.dstate = S, Dm, L, N
-    a.ngroups = ngroups
-    a.batch_per_dir = batch_per_dir
-    a.io_dtype = dtype_code(u)
-    a.bc_dtype = dtype_code(Bm)
-    a.flags = flags
-    a.ckpt_every = ckpt_every
-    a.ckpt_dtype = _ckpt_dtype_code(ckpt)
-    a.u, a.delta, a.z, a.dout = _ptr(u), _ptr(delta), _ptr(z), _ptr(dout)
-    a.B, a.C, a.A, a.D, a.delta_bias = _ptr(Bm), _ptr(Cm), _ptr(A32), _ptr(D32), _ptr(b32)
-    a.z_row_index, a.out_row_index = _ptr(z_row_index), _ptr(out_row_index)
-    a.ckpt = _ptr(ckpt)
+    a.dout = _ptr(dout)
     a.du, a.ddelta, a.dz = _ptr(du), _ptr(ddelta), _ptr(dz)
     a.dBC_partial, a.dA_partial = _ptr(dBC), _ptr(dA)
     a.dD_partial, a.dbias_partial = _ptr(dD), _ptr(dbias)
-    a.u_ss, a.u_sl, a.u_sd = u.stride()
-    a.dt_ss, a.dt_sl, a.dt_sd = delta.stride()
     if z is not None:
-        a.z_ss, a.z_sl, a.z_sd = z.stride()
         a.dz_ss, a.dz_sl, a.dz_sd = dz.stride()
     a.do_ss, a.do_sl, a.do_sd = dout.stride()
-    a.B_ss, a.B_sl, a.B_sn = Bm.stride()
-    a.C_ss, a.C_sl, a.C_sn = Cm.stride()
-    a.B_sg = a.C_sg = N
     a.du_ss, a.du_sl, a.du_sd = du.stride()
     a.ddt_ss, a.ddt_sl, a.ddt_sd = ddelta.stride()
     nbytes = scan_bwd_algorithmic_bytes(S, Dm, L, N, u.element_size(), z is not None)
@@ -451,16 +437,23 @@ def _colsum_launch(x):
     return out
 
 
-def gather_conv1d_fwd(x, weight, bias, *, row_index=None, ndir=1, silu=True, out=None):
-    """x: [B, L, Dm] token-major view (e.g. xz[..., :Dm]); weight [Dm, W]; -> [ndir*B, L, Dm]."""
-    _require_gpu(x, weight, bias)
-    Bsz, L, Dm = x.shape
+def _conv_params(x, weight, bias):
+    """The conv parameters as the kernels read them: weight [Dm, W] contiguous, fp32 unless it shares x's dtype; bias in the weight's
+    dtype.  Returns (weight, bias, W)."""
     W = weight.shape[-1]
-    weight = weight.reshape(Dm, W).contiguous()
+    weight = weight.reshape(x.shape[-1], W).contiguous()
     if weight.dtype != x.dtype and weight.dtype != torch.float32:
         weight = weight.float()
     if bias is not None:
         bias = bias.to(weight.dtype).contiguous()
+    return weight, bias, W
+
+
+def gather_conv1d_fwd(x, weight, bias, *, row_index=None, ndir=1, silu=True, out=None):
+    """x: [B, L, Dm] token-major view (e.g. xz[..., :Dm]); weight [Dm, W]; -> [ndir*B, L, Dm]."""
+    _require_gpu(x, weight, bias)
+    Bsz, L, Dm = x.shape
+    weight, bias, W = _conv_params(x, weight, bias)
     if out is None:
         out = torch.empty((ndir * Bsz, L, Dm), dtype=x.dtype, device=x.device)
     a = dm_conv_fwd_args()
@@ -497,13 +490,8 @@ def gather_conv1d_xproj_fwd(x, weight, bias, wx, *, row_index=None, ndir=1, silu
     Returns (xc [ndir*B, L, Dm] = SiLU(conv(gathered x)), x_dbl [ndir*B*L, P] = xc @ wx^T) from ONE kernel."""
     _require_gpu(x, weight, bias, wx)
     Bsz, L, Dm = x.shape
-    W = weight.shape[-1]
     P = wx.shape[0]
-    weight = weight.reshape(Dm, W).contiguous()
-    if weight.dtype != x.dtype and weight.dtype != torch.float32:
-        weight = weight.float()
-    if bias is not None:
-        bias = bias.to(weight.dtype).contiguous()
+    weight, bias, W = _conv_params(x, weight, bias)
     wx = wx.contiguous()
     assert wx.dtype == x.dtype and wx.shape[1] == Dm
     out = torch.empty((ndir * Bsz, L, Dm), dtype=x.dtype, device=x.device)
@@ -561,13 +549,8 @@ def gather_conv1d_xproj_bwd(x, weight, bias, du, dxdbl, wxt, *, row_index=None, 
     directions of a sample, the first stores, the others read-add-store)."""
     _require_gpu(x, weight, bias, du, dxdbl, wxt)
     Bsz, L, Dm = x.shape
-    W = weight.shape[-1]
     P = wxt.shape[1]
-    weight = weight.reshape(Dm, W).contiguous()
-    if weight.dtype != x.dtype and weight.dtype != torch.float32:
-        weight = weight.float()
-    if bias is not None:
-        bias = bias.to(weight.dtype).contiguous()
+    weight, bias, W = _conv_params(x, weight, bias)
     wxt = wxt.contiguous()
     assert wxt.dtype == x.dtype and wxt.shape[0] == Dm and dxdbl.dtype == x.dtype and du.dtype == x.dtype
     assert dxdbl.stride(1) == 1 and du.stride(2) == 1
@@ -613,12 +596,7 @@ def gather_conv1d_bwd(x, weight, bias, dout, *, row_index=None, ndir=1, silu=Tru
     """Returns (dx_slabs [ndir*B, L, Dm] in token order, dweight [Dm, W] fp32, dbias [Dm] fp32)."""
     _require_gpu(x, weight, bias, dout)
     Bsz, L, Dm = x.shape
-    W = weight.shape[-1]
-    weight = weight.reshape(Dm, W).contiguous()
-    if weight.dtype != x.dtype and weight.dtype != torch.float32:
-        weight = weight.float()
-    if bias is not None:
-        bias = bias.to(weight.dtype).contiguous()
+    weight, bias, W = _conv_params(x, weight, bias)
     lib = _lib.load()
     nchunk = lib.dm_conv_nchunk(L)
     dev = x.device

@@ -164,7 +164,7 @@ class Mamba(nn.Module):
 
 def forward_pair(mix0: Mamba, mix1: Mamba, x0, x1):
     """(mix0(x0, 'spiral'), mix1(x1, 'spiral')) -- the two mixers of a DiffMa block (reference block/mamba_block.py:107-108) -- with
-    every stage launched once for both when the call pattern allows it (selective_scan_interface._SpiralSSMPairFn), else one after
+    every stage launched once for both when the call pattern allows it (selective_scan_interface._SpiralSSMFn with G = 2), else one after
     the other.  Same arithmetic per mixer either way."""
     if not (isinstance(mix0, Mamba) and isinstance(mix1, Mamba) and x0.is_cuda and x0.shape == x1.shape and x0.dtype == x1.dtype
             and mix0.in_proj.bias is None and mix1.in_proj.bias is None and mix0.out_proj.bias is None and mix1.out_proj.bias is None

@@ -338,138 +338,6 @@ def linear_splitk(x, weight, bias=None):
 
 
 # ------------------------------------------------------------------------------------------------
-# Fused 3-direction operator of the DiffMa mixer
-# ------------------------------------------------------------------------------------------------
-# DIFFMA_HOIST_GATE=0: gate (and softplus) back inside every per-direction scan, as upstream evaluates them (A/B runs, tests)
-HOIST_GATE = os.environ.get("DIFFMA_HOIST_GATE", "1") == "1"
-
-
-class _SpiralSSMFn(torch.autograd.Function):
-    """xz [B, L, 2*Din] token-major -> merged pre-projection output y [B, L, Din].
-
-    scan_index [ndir, L]: position l of direction k reads token scan_index[k][l]   (CrossScan, block/mamba.py:41-45)
-    Because CrossMerge adds direction k's output row origina_k[t] at token t and origina_k is the inverse
-    permutation of scan_index[k] (tools.py:38-42), step l's result belongs to token scan_index[k][l]: the
-    same table drives the gather of x and z and the scatter of y.
-    """
-
-    @staticmethod
-    def forward(ctx, xz, conv_w, conv_b, Wx, Wdt, dt_bias, A, Dskip, scan_index, grad_on=True, out_index=None, merge=True):
-        """out_index (default: scan_index): row of the per-direction output that step l's result is written to -- the
-        baseline blocks need a scatter that is not the gather's inverse (ViM, block/mamba.py:362-367).  merge=False returns
-        the per-direction outputs [ndir, B, L, Din] instead of their sum."""
-        Bsz, L, D2 = xz.shape
-        Din = D2 // 2
-        ndir = scan_index.shape[0]
-        R = Wdt.shape[1]
-        N = A.shape[1]
-        dt_ = xz.dtype
-        x_view, z_view = xz[..., :Din], xz[..., Din:]
-        need_grad = grad_on and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[1:8]))   # grad_on: the caller's grad mode
-        Wx_c, Wdt_c = cast_weight(Wx, dt_), cast_weight(Wdt, dt_)              # kept for the backward (the step's shadows, or one cast per step)
-        if hip_ops.conv_xproj_supported(x_view, Wx_c, ndir * Bsz, conv_w.shape[-1]):
-            # gather + conv + SiLU + x_proj in one kernel: x~ is projected while its tile is still on the CU
-            xc, x_dbl = hip_ops.gather_conv1d_xproj_fwd(x_view, conv_w, conv_b, Wx_c, row_index=scan_index, ndir=ndir, silu=True)
-        else:
-            xc = hip_ops.gather_conv1d_fwd(x_view, conv_w, conv_b, row_index=scan_index, ndir=ndir, silu=True)   # [ndir*B, L, Din]
-            x_dbl = GemmChain.run(F.linear, xc.view(-1, Din), Wx_c)            # [ndir*B*L, R+2N]
-        # Hoisted gate: CrossScan permutes x and z together and CrossMerge applies the inverse permutation (block/mamba.py:41-45,
-        # 66-68), so merged[t] = silu(z[t]) * sum_k y~_k[t]: the scans run WITHOUT z and the gate is applied once per token by the
-        # merge (one z read in an HBM-bound kernel) instead of three times inside the VALU-bound scans.  Needs the scatter table
-        # to be the gather table (not ViM's) and a merge to ride on.
-        # One direction (the reference's own three-calls-per-mixer pattern through mamba_inner_fn, the ZigMa order): the gate pass is an
-        # extra launch, worth it only where the scans are VALU-bound -- the large launches (K2 1 058 -> ~830 us per 512 sequences).
-        hoist = HOIST_GATE and merge and out_index is None and (ndir > 1 or Bsz >= hip_ops.XPROJ_FUSED_MIN_SEQS)
-        # Hoisted softplus: delta = softplus(dt_proj(.) + bias) leaves the dt_proj kernel activated (csrc/dtproj.hip) and the scans
-        # run with DM_FLAG_DELTA_ACTIVATED (forward: nothing to evaluate; backward: only 1 - exp(-delta)).
-        # The backward of that flag exists for d_state 16 only (csrc/scan_bwd.hip): other widths keep the softplus inside the scans.
-        act = hoist and N == 16 and hip_ops.dtproj_softplus_supported(x_dbl, Wdt_c)
-        if act:
-            delta = hip_ops.dtproj_softplus_fwd(x_dbl, Wdt_c, dt_bias).view(ndir * Bsz, L, Din)
-        else:
-            delta = GemmChain.run(F.linear, x_dbl[:, :R], Wdt_c).view(ndir * Bsz, L, Din)
-        xd3 = x_dbl.view(ndir * Bsz, L, R + 2 * N)
-        Bm, Cm = xd3[..., R:R + N], xd3[..., R + N:]
-        ckpt = None
-        if need_grad:
-            ckpt = hip_ops.alloc_scan_ckpt(ndir * Bsz, L, N, Din, xz.dtype, xz.device)
-        oidx = scan_index if out_index is None else out_index
-        ctx.merge, ctx.hoist, ctx.act = merge, hoist, act
-        if hoist:
-            ydir = hip_ops.scan_fwd(xc, delta, A, Bm, Cm, Dskip, None, dt_bias, True, z_row_index=scan_index, out_row_index=oidx,
-                                    batch_per_dir=Bsz, ckpt=ckpt, delta_activated=act)          # token order, NOT gated
-            pre = torch.empty((Bsz, L, Din), dtype=dt_, device=xz.device) if need_grad else None   # ungated sum, kept for dz
-            y = hip_ops.token_merge(ydir.view(ndir, Bsz, L, Din), gate=z_view, pre_out=pre)
-            ctx.save_for_backward(xz, conv_w, conv_b, Wx, Wdt, dt_bias, A, Dskip, scan_index, xc, x_dbl, delta, ckpt, Wx_c, Wdt_c, oidx, pre)
-            return y
-        ydir = hip_ops.scan_fwd(xc, delta, A, Bm, Cm, Dskip, z_view, dt_bias, True, z_row_index=scan_index,
-                                out_row_index=oidx, batch_per_dir=Bsz, ckpt=ckpt)                   # token order
-        ctx.save_for_backward(xz, conv_w, conv_b, Wx, Wdt, dt_bias, A, Dskip, scan_index, xc, x_dbl, delta, ckpt, Wx_c, Wdt_c, oidx, None)
-        if not merge:
-            return ydir.view(ndir, Bsz, L, Din)
-        return hip_ops.token_merge(ydir.view(ndir, Bsz, L, Din)) if ndir > 1 else ydir
-
-    @staticmethod
-    def backward(ctx, dy):
-        xz, conv_w, conv_b, Wx, Wdt, dt_bias, A, Dskip, scan_index, xc, x_dbl, delta, ckpt, Wx_c, Wdt_c, oidx, pre = ctx.saved_tensors
-        Bsz, L, D2 = xz.shape
-        Din = D2 // 2
-        ndir = scan_index.shape[0]
-        R = Wdt.shape[1]
-        N = A.shape[1]
-        dt_ = xz.dtype
-        dy = dy.contiguous()
-        if dy.dtype != dt_:
-            dy = dy.to(dt_)
-        if not ctx.merge:
-            dy = dy.view(ndir * Bsz, L, Din)           # one gradient per direction
-        xd3 = x_dbl.view(ndir * Bsz, L, R + 2 * N)
-        Bm, Cm = xd3[..., R:R + N], xd3[..., R + N:]
-        z_view = xz[..., Din:]
-        M = ndir * Bsz * L
-        dx_dbl = torch.empty((M, R + 2 * N), dtype=dt_, device=xz.device)
-        dxz = torch.empty_like(xz)
-        if ctx.hoist:
-            # the gate's backward once per token: g = dy * silu(z) is what the three directions read as their output gradient,
-            # dz = dy * pre * silu'(z) goes straight into the z half of d(xz) (no dz slabs, no 3-slab merge)
-            g, dz = hip_ops.gate_bwd(dy, z_view, pre, dz_out=dxz[..., Din:])
-            du, ddelta, _, _, _, dA, dD, dbias = hip_ops.scan_bwd(
-                xc, delta, A, Bm, Cm, Dskip, None, dt_bias, g, ckpt, True, z_row_index=scan_index, out_row_index=oidx,
-                batch_per_dir=Bsz, dbc_out=dx_dbl.view(ndir * Bsz, L, R + 2 * N)[..., R:], delta_activated=ctx.act)
-        else:
-            du, ddelta, dz, _, _, dA, dD, dbias = hip_ops.scan_bwd(
-                xc, delta, A, Bm, Cm, Dskip, z_view, dt_bias, dy, ckpt, True, z_row_index=scan_index,
-                out_row_index=oidx, batch_per_dir=Bsz, dout_per_seq=not ctx.merge,
-                dbc_out=dx_dbl.view(ndir * Bsz, L, R + 2 * N)[..., R:])      # dB | dC land in their x_dbl columns
-        ddelta2 = ddelta.view(M, Din)
-        if hip_ops.dtproj_bwd_supported(ddelta2, x_dbl, Wdt_c, dx_dbl):
-            # both consumers of ddelta -- the dt columns of d(x_dbl) and dW_dt -- in ONE read of it (csrc/dtproj.hip, K8b)
-            dWdt = hip_ops.dtproj_bwd(ddelta2, x_dbl, Wdt_c, dx_dbl).to(Wdt.dtype)
-        else:
-            dx_dbl[:, :R] = GemmChain.run(torch.mm, ddelta2, Wdt_c)        # (a strided `out=` is an untuned GEMM shape class: pathologically slow by default)
-            dWdt = _tn_splitk(ddelta2, x_dbl[:, :R]).to(Wdt.dtype)               # [Din, R]; the dt columns of x_dbl in place (leading dimension R + 2N)
-        dWx = _tn_splitk(dx_dbl, xc.view(M, Din)).to(Wx.dtype)                   # [R+2N, Din]
-        if hip_ops.conv_xproj_bwd_supported(xz[..., :Din], Wx_c, ndir * Bsz, conv_w.shape[-1], du, dx_dbl):
-            # d x~ = du + dx_dbl @ Wx is formed tile by tile inside the conv backward (K4x) instead of by an addmm over [M, Din]
-            merged_dx = hip_ops.DX_MERGED and conv_w.shape[-1] == 4         # one direction: dx straight into d(xz), no copy pass
-            dx_slabs, dconv_w, dconv_b = hip_ops.gather_conv1d_xproj_bwd(xz[..., :Din], conv_w, conv_b, du, dx_dbl, Wx_c.t().contiguous(),
-                                                                         row_index=scan_index, ndir=ndir, silu=True,
-                                                                         merged_out=dxz[..., :Din] if merged_dx else None)
-        else:
-            merged_dx = False
-            # in place: an out-of-place addmm first copies `du` into its result (a 2 x 308 MB device memcpy per call)
-            dxc = GemmChain.run(du.view(M, Din).addmm_, dx_dbl, Wx_c).view(ndir * Bsz, L, Din)
-            dx_slabs, dconv_w, dconv_b = hip_ops.gather_conv1d_bwd(xz[..., :Din], conv_w, conv_b, dxc,
-                                                                   row_index=scan_index, ndir=ndir, silu=True)
-        if not merged_dx:                                          # K4x already summed the directions into dxz[..., :Din]
-            hip_ops.token_merge(dx_slabs.view(ndir, Bsz, L, Din), out=dxz[..., :Din])
-        if not ctx.hoist:
-            hip_ops.token_merge(dz.view(ndir, Bsz, L, Din), out=dxz[..., Din:])
-        return (dxz, dconv_w.to(conv_w.dtype).reshape(conv_w.shape), dconv_b.to(conv_b.dtype) if conv_b is not None else None,
-                dWx, dWdt, dbias.to(dt_bias.dtype), dA.to(A.dtype), dD.to(Dskip.dtype), None, None, None, None)
-
-
-# ------------------------------------------------------------------------------------------------
 # The TWO mixers of a DiffMa block as one set of launches (reference block/mamba_block.py:107-108)
 # ------------------------------------------------------------------------------------------------
 # The reference runs mamba1(x_ssm) and mamba2(w_ssm) one after the other: same shapes, different weights and spiral tables.  Its own
@@ -563,104 +431,179 @@ def linear_pair(x0, x1, W0, W1):
     return _LinearPairFn.apply(x0, x1, W0, W1)
 
 
-class _SpiralSSMPairFn(torch.autograd.Function):
-    """_SpiralSSMFn for the two mixers of a block at once (hoisted gate + hoisted softplus, 16-bit I/O, d_state 16, small launches):
-    xz0, xz1 [B, L, 2*Din] -> (y0, y1) [B, L, Din], every kernel stage launched once for both."""
+# ------------------------------------------------------------------------------------------------
+# Fused 3-direction operator of the DiffMa mixer: one mixer, or the two mixers of a block in one set of launches
+# ------------------------------------------------------------------------------------------------
+# DIFFMA_HOIST_GATE=0: gate (and softplus) back inside every per-direction scan, as upstream evaluates them (A/B runs, tests)
+HOIST_GATE = os.environ.get("DIFFMA_HOIST_GATE", "1") == "1"
+
+
+def _inner_on_own(G, M, a, b, a_kmajor, b_kmajor, out_dtype=None):
+    """The operator's inner projections (x_proj forward, dWx, du += dx_dbl @ Wx) on dm_gemm: a choice of the pair alone; the single
+    mixer keeps them on the library.  (64-column products: the own kernel holds up to ~4x the rows.)"""
+    return G == 2 and _pair_use_own(M // 4, a, b, a_kmajor, b_kmajor, out_dtype)
+
+
+class _SpiralSSMFn(torch.autograd.Function):
+    """xz [B, L, 2*Din] token-major -> merged pre-projection output y [B, L, Din], for G = 1 mixer or for the G = 2 mixers of a block
+    at once.  The per-mixer operands arrive field by field, G of each; every kernel stage runs through `stage`: hip_ops.both for the
+    pair (ONE launch for both mixers), the plain call for one mixer.  Results that the pair shares as halves of one allocation
+    (xc, x_dbl, y, pre, du, dx_dbl, dxz) are [G, ...] buffers either way.
+
+    scan_index [ndir, L]: position l of direction k reads token scan_index[k][l]   (CrossScan, block/mamba.py:41-45)
+    Because CrossMerge adds direction k's output row origina_k[t] at token t and origina_k is the inverse
+    permutation of scan_index[k] (tools.py:38-42), step l's result belongs to token scan_index[k][l]: the
+    same table drives the gather of x and z and the scatter of y.
+
+    The pair (spiral_ssm_pair_supported) is one arm of what follows: hoisted gate + hoisted softplus, unfused conv, 16-bit I/O,
+    d_state 16, small launches.
+    """
+    NFIELD = 9             # xz, scan_index, conv_w, conv_b, Wx, Wdt, dt_bias, A, Dskip
 
     @staticmethod
-    def forward(ctx, xz0, xz1, idx0, idx1, grad_on, cw0, cw1, cb0, cb1, Wx0, Wx1, Wdt0, Wdt1, b0, b1, A0, A1, D0, D1):
-        Bsz, L, D2 = xz0.shape
+    def _stage(G):
+        return hip_ops.both if G == 2 else (lambda fn: (fn(0),))
+
+    @staticmethod
+    def forward(ctx, grad_on, out_index, merge, G, *ops):
+        """out_index (default: scan_index): row of the per-direction output that step l's result is written to -- the
+        baseline blocks need a scatter that is not the gather's inverse (ViM, block/mamba.py:362-367).  merge=False returns
+        the per-direction outputs [ndir, B, L, Din] instead of their sum.  Returns a tuple of G outputs."""
+        xz, idx, cw, cb, Wx, Wdt, bias, A, Dk = (ops[i * G:(i + 1) * G] for i in range(_SpiralSSMFn.NFIELD))
+        stage, each = _SpiralSSMFn._stage(G), range(G)
+        Bsz, L, D2 = xz[0].shape
         Din = D2 // 2
-        ndir = idx0.shape[0]
-        R, N = Wdt0.shape[1], A0.shape[1]
+        ndir = idx[0].shape[0]
+        R, N = Wdt[0].shape[1], A[0].shape[1]
         S, M = ndir * Bsz, ndir * Bsz * L
-        dt_, dev = xz0.dtype, xz0.device
-        need_grad = grad_on and any(ctx.needs_input_grad)
-        xz, idx = (xz0, xz1), (idx0, idx1)
-        cw, cb, bias, A, Dk = (cw0, cw1), (cb0, cb1), (b0, b1), (A0, A1), (D0, D1)
-        Wx_st, Wdt_st = stacked_pair(Wx0, Wx1, dt_), stacked_pair(Wdt0, Wdt1, dt_)       # [2, R+2N, Din], [2, Din, R]
-        xc = torch.empty((2, S, L, Din), dtype=dt_, device=dev)
-        hip_ops.both(lambda g: hip_ops.gather_conv1d_fwd(xz[g][..., :Din], cw[g], cb[g], row_index=idx[g], ndir=ndir, silu=True, out=xc[g]))
-        # x_proj stays one product per mixer: as a batch-2 GEMM its [M, 1024] x [1024, 64] shape makes TunableOp's first-use tuning
-        # run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop, DESIGN.md section 7);
-        # the plain products below are the ones the unpaired path has always issued
-        x_dbl = torch.empty((2, M, R + 2 * N), dtype=dt_, device=dev)
-        xc2 = xc.view(2, M, Din)
-        if _pair_use_own(M // 4, xc2[0], Wx_st[0], True, True):        # (a 64-column product: the own kernel holds up to ~4x the rows)
-            _own_pair(xc2, Wx_st, True, True, x_dbl)
+        dt_, dev = xz[0].dtype, xz[0].device
+        need_grad = grad_on and any(ctx.needs_input_grad)                      # grad_on: the caller's grad mode
+        # kept for the backward, indexed by mixer: the pair's shared shadow buffer (no launch), else the step's shadow or one cast per step
+        if G == 2:
+            Wx_c, Wdt_c = stacked_pair(Wx[0], Wx[1], dt_), stacked_pair(Wdt[0], Wdt[1], dt_)    # [2, R+2N, Din], [2, Din, R]
         else:
-            for g in (0, 1):
-                GemmChain.run(torch.mm, xc2[g], Wx_st[g].t(), out=x_dbl[g])
-        delta = hip_ops.both(lambda g: hip_ops.dtproj_softplus_fwd(x_dbl[g], Wdt_st[g], bias[g]).view(S, L, Din))
-        ckpt = [hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev) if need_grad else None for _ in (0, 1)]
-        xd3 = x_dbl.view(2, S, L, R + 2 * N)
-        ydir = hip_ops.both(lambda g: hip_ops.scan_fwd(
-            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], True,
-            z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, ckpt=ckpt[g], delta_activated=True))
-        y = torch.empty((2, Bsz, L, Din), dtype=dt_, device=dev)
-        pre = torch.empty((2, Bsz, L, Din), dtype=dt_, device=dev) if need_grad else None
-        hip_ops.both(lambda g: hip_ops.token_merge(ydir[g].view(ndir, Bsz, L, Din), gate=xz[g][..., Din:],
-                                                   pre_out=None if pre is None else pre[g], out=y[g]))
+            Wx_c, Wdt_c = cast_weight(Wx[0], dt_)[None], cast_weight(Wdt[0], dt_)[None]
+        if hip_ops.conv_xproj_supported(xz[0][..., :Din], Wx_c[0], S, cw[0].shape[-1]):
+            # gather + conv + SiLU + x_proj in one kernel: x~ is projected while its tile is still on the CU
+            xc, x_dbl = zip(*stage(lambda g: hip_ops.gather_conv1d_xproj_fwd(xz[g][..., :Din], cw[g], cb[g], Wx_c[g], row_index=idx[g],
+                                                                             ndir=ndir, silu=True)))
+        else:
+            xc = torch.empty((G, S, L, Din), dtype=dt_, device=dev)
+            stage(lambda g: hip_ops.gather_conv1d_fwd(xz[g][..., :Din], cw[g], cb[g], row_index=idx[g], ndir=ndir, silu=True, out=xc[g]))
+            # x_proj is one product per mixer: as a batch-2 GEMM its [M, 1024] x [1024, 64] shape makes TunableOp's first-use tuning
+            # run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop, DESIGN.md section 7)
+            if _inner_on_own(G, M, xc[0].view(M, Din), Wx_c[0], True, True):
+                x_dbl = _own_pair(xc.view(G, M, Din), Wx_c, True, True, torch.empty((G, M, R + 2 * N), dtype=dt_, device=dev))
+            else:
+                x_dbl = [GemmChain.run(F.linear, xc[g].view(M, Din), Wx_c[g]) for g in each]          # [ndir*B*L, R+2N]
+        # Hoisted gate: CrossScan permutes x and z together and CrossMerge applies the inverse permutation (block/mamba.py:41-45,
+        # 66-68), so merged[t] = silu(z[t]) * sum_k y~_k[t]: the scans run WITHOUT z and the gate is applied once per token by the
+        # merge (one z read in an HBM-bound kernel) instead of three times inside the VALU-bound scans.  Needs the scatter table
+        # to be the gather table (not ViM's) and a merge to ride on.
+        # One direction (the reference's own three-calls-per-mixer pattern through mamba_inner_fn, the ZigMa order): the gate pass is an
+        # extra launch, worth it only where the scans are VALU-bound -- the large launches (K2 1 058 -> ~830 us per 512 sequences).
+        hoist = HOIST_GATE and merge and out_index is None and (ndir > 1 or Bsz >= hip_ops.XPROJ_FUSED_MIN_SEQS)
+        # Hoisted softplus: delta = softplus(dt_proj(.) + bias) leaves the dt_proj kernel activated (csrc/dtproj.hip) and the scans
+        # run with DM_FLAG_DELTA_ACTIVATED (forward: nothing to evaluate; backward: only 1 - exp(-delta)).
+        # The backward of that flag exists for d_state 16 only (csrc/scan_bwd.hip): other widths keep the softplus inside the scans.
+        act = hoist and N == 16 and hip_ops.dtproj_softplus_supported(x_dbl[0], Wdt_c[0])
+        assert G == 1 or act, "the pair path is built for the hoisted gate with the activated delta (spiral_ssm_pair_supported)"
+        if act:
+            delta = stage(lambda g: hip_ops.dtproj_softplus_fwd(x_dbl[g], Wdt_c[g], bias[g]).view(S, L, Din))
+        else:
+            delta = [GemmChain.run(F.linear, x_dbl[g][:, :R], Wdt_c[g]).view(S, L, Din) for g in each]
+        ckpt = [hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev) if need_grad else None for _ in each]
+        oidx = idx if out_index is None else (out_index,)
+        xd3 = [t.view(S, L, R + 2 * N) for t in x_dbl]
+        ydir = stage(lambda g: hip_ops.scan_fwd(                               # token order; gated here unless the merge does it
+            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None if hoist else xz[g][..., Din:], bias[g], True,
+            z_row_index=idx[g], out_row_index=oidx[g], batch_per_dir=Bsz, ckpt=ckpt[g], delta_activated=act))
+        pre = None
+        if hoist:
+            y = torch.empty((G, Bsz, L, Din), dtype=dt_, device=dev)
+            pre = torch.empty((G, Bsz, L, Din), dtype=dt_, device=dev) if need_grad else None          # ungated sum, kept for dz
+            stage(lambda g: hip_ops.token_merge(ydir[g].view(ndir, Bsz, L, Din), gate=xz[g][..., Din:],
+                                                pre_out=None if pre is None else pre[g], out=y[g]))
+            out = tuple(y)
+        elif not merge:
+            out = tuple(t.view(ndir, Bsz, L, Din) for t in ydir)
+        else:
+            out = tuple(hip_ops.token_merge(t.view(ndir, Bsz, L, Din)) if ndir > 1 else t for t in ydir)
         if need_grad:
-            ctx.save_for_backward(xz0, xz1, idx0, idx1, cw0, cw1, cb0, cb1, b0, b1, A0, A1, D0, D1, Wx_st, Wdt_st, xc, x_dbl,
-                                  delta[0], delta[1], ckpt[0], ckpt[1], pre)
-            ctx.meta = (Wx0.dtype, Wdt0.dtype)
-        return y[0], y[1]
+            ctx.save_for_backward(*xz, *idx, *oidx, *cw, *cb, *bias, *A, *Dk, *xc, *x_dbl, *delta, *ckpt,
+                                  *((None,) * G if pre is None else pre), Wx_c, Wdt_c)
+            ctx.meta = (G, merge, hoist, act, Wx[0].dtype, Wdt[0].dtype)
+        return out
 
     @staticmethod
-    def backward(ctx, dy0, dy1):
-        (xz0, xz1, idx0, idx1, cw0, cw1, cb0, cb1, b0, b1, A0, A1, D0, D1, Wx_st, Wdt_st, xc, x_dbl, dl0, dl1, ck0, ck1, pre) = ctx.saved_tensors
-        wx_dt, wdt_dt = ctx.meta
-        Bsz, L, D2 = xz0.shape
+    def backward(ctx, *dys):
+        G, merge, hoist, act, wx_dt, wdt_dt = ctx.meta
+        sv = ctx.saved_tensors
+        xz, idx, oidx, cw, cb, bias, A, Dk, xc, x_dbl, delta, ckpt, pre = (sv[i * G:(i + 1) * G] for i in range(13))
+        Wx_c, Wdt_c = sv[-2:]
+        stage, each = _SpiralSSMFn._stage(G), range(G)
+        Bsz, L, D2 = xz[0].shape
         Din = D2 // 2
-        ndir = idx0.shape[0]
-        R, N = Wdt_st.shape[2], A0.shape[1]
+        ndir = idx[0].shape[0]
+        R, N = Wdt_c.shape[2], A[0].shape[1]
         S, M = ndir * Bsz, ndir * Bsz * L
-        dt_, dev = xz0.dtype, xz0.device
-        xz, idx, delta, ckpt = (xz0, xz1), (idx0, idx1), (dl0, dl1), (ck0, ck1)
-        cw, cb, bias, A, Dk = (cw0, cw1), (cb0, cb1), (b0, b1), (A0, A1), (D0, D1)
-        dy = [t.contiguous() if t.dtype == dt_ else t.contiguous().to(dt_) for t in (dy0, dy1)]
-        dxz = torch.empty((2, Bsz, L, D2), dtype=dt_, device=dev)
-        dx_dbl = torch.empty((2, M, R + 2 * N), dtype=dt_, device=dev)
-        xd3 = x_dbl.view(2, S, L, R + 2 * N)
-        gate_g = hip_ops.both(lambda g: hip_ops.gate_bwd(dy[g], xz[g][..., Din:], pre[g], dz_out=dxz[g][..., Din:])[0])
-        du = torch.empty((2, S, L, Din), dtype=dt_, device=dev)
-        res = hip_ops.both(lambda g: hip_ops.scan_bwd(
-            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None, bias[g], gate_g[g], ckpt[g], True,
-            z_row_index=idx[g], out_row_index=idx[g], batch_per_dir=Bsz, du_out=du[g],
-            dbc_out=dx_dbl[g].view(S, L, R + 2 * N)[..., R:], delta_activated=True))
-        ddelta = [res[g][1].view(M, Din) for g in (0, 1)]
-        if hip_ops.dtproj_bwd_supported(ddelta[0], x_dbl[0], Wdt_st[0], dx_dbl[0]):
-            dWdt = hip_ops.both(lambda g: hip_ops.dtproj_bwd(ddelta[g], x_dbl[g], Wdt_st[g], dx_dbl[g]))
+        dt_, dev = xz[0].dtype, xz[0].device
+        dy = [t.contiguous().to(dt_) for t in dys]
+        if not merge:
+            dy = [t.view(S, L, Din) for t in dy]           # one gradient per direction
+        dxz = torch.empty((G, Bsz, L, D2), dtype=dt_, device=dev)
+        dx_dbl = torch.empty((G, M, R + 2 * N), dtype=dt_, device=dev)
+        du = torch.empty((G, S, L, Din), dtype=dt_, device=dev)
+        xd3 = [t.view(S, L, R + 2 * N) for t in x_dbl]
+        if hoist:
+            # the gate's backward once per token: g = dy * silu(z) is what the three directions read as their output gradient,
+            # dz = dy * pre * silu'(z) goes straight into the z half of d(xz) (no dz slabs, no 3-slab merge)
+            gy = stage(lambda g: hip_ops.gate_bwd(dy[g], xz[g][..., Din:], pre[g], dz_out=dxz[g][..., Din:])[0])
+        else:
+            gy = dy
+        res = stage(lambda g: hip_ops.scan_bwd(
+            xc[g], delta[g], A[g], xd3[g][..., R:R + N], xd3[g][..., R + N:], Dk[g], None if hoist else xz[g][..., Din:], bias[g], gy[g],
+            ckpt[g], True, z_row_index=idx[g], out_row_index=oidx[g], batch_per_dir=Bsz, dout_per_seq=not merge, du_out=du[g],
+            dbc_out=dx_dbl[g].view(S, L, R + 2 * N)[..., R:], delta_activated=act))        # dB | dC land in their x_dbl columns
+        ddelta = [r[1].view(M, Din) for r in res]
+        if hip_ops.dtproj_bwd_supported(ddelta[0], x_dbl[0], Wdt_c[0], dx_dbl[0]):
+            # both consumers of ddelta -- the dt columns of d(x_dbl) and dW_dt -- in ONE read of it (csrc/dtproj.hip, K8b)
+            dWdt = stage(lambda g: hip_ops.dtproj_bwd(ddelta[g], x_dbl[g], Wdt_c[g], dx_dbl[g]))
         else:
             dWdt = []
-            for g in (0, 1):
-                dx_dbl[g][:, :R] = GemmChain.run(torch.mm, ddelta[g], Wdt_st[g])
-                dWdt.append(_tn_splitk(ddelta[g], x_dbl[g][:, :R]))
-        xc2 = xc.view(2, M, Din)
-        if _pair_use_own(M // 4, dx_dbl[0], xc2[0], False, False, torch.float32):
-            dWx = _own_pair(dx_dbl, xc2, False, False, torch.empty((2, R + 2 * N, Din), dtype=torch.float32, device=dev))
+            for g in each:
+                dx_dbl[g][:, :R] = GemmChain.run(torch.mm, ddelta[g], Wdt_c[g])   # (a strided `out=` is an untuned GEMM shape class: pathologically slow by default)
+                dWdt.append(_tn_splitk(ddelta[g], x_dbl[g][:, :R]))               # [Din, R]; the dt columns of x_dbl in place (leading dimension R + 2N)
+        xc2 = [t.view(M, Din) for t in xc]
+        if _inner_on_own(G, M, dx_dbl[0], xc2[0], False, False, torch.float32):
+            dWx = _own_pair(dx_dbl, xc2, False, False, torch.empty((G, R + 2 * N, Din), dtype=torch.float32, device=dev))
         else:
-            dWx = [_tn_splitk(dx_dbl[g], xc2[g]) for g in (0, 1)]                          # [R+2N, Din] fp32 each
-        du2 = du.view(2, M, Din)
-        if _pair_use_own(M // 4, dx_dbl[0], Wx_st[0], True, False):
-            _own_pair(dx_dbl, Wx_st, True, False, du2, accumulate=True)                    # d x~ = du + dx_dbl @ Wx, in place, one launch
+            dWx = [_tn_splitk(dx_dbl[g], xc2[g]) for g in each]                   # [R+2N, Din] fp32 each
+        if hip_ops.conv_xproj_bwd_supported(xz[0][..., :Din], Wx_c[0], S, cw[0].shape[-1], du[0], dx_dbl[0]):
+            # d x~ = du + dx_dbl @ Wx is formed tile by tile inside the conv backward (K4x) instead of by an addmm over [M, Din]
+            merged_dx = hip_ops.DX_MERGED and cw[0].shape[-1] == 4      # one direction: dx straight into d(xz), no copy pass
+            cres = stage(lambda g: hip_ops.gather_conv1d_xproj_bwd(xz[g][..., :Din], cw[g], cb[g], du[g], dx_dbl[g], Wx_c[g].t().contiguous(),
+                                                                   row_index=idx[g], ndir=ndir, silu=True,
+                                                                   merged_out=dxz[g][..., :Din] if merged_dx else None))
         else:
-            for g in (0, 1):
-                GemmChain.run(du2[g].addmm_, dx_dbl[g], Wx_st[g])
-        dxc = du
-        cres = hip_ops.both(lambda g: hip_ops.gather_conv1d_bwd(xz[g][..., :Din], cw[g], cb[g], dxc[g], row_index=idx[g], ndir=ndir, silu=True))
-        hip_ops.both(lambda g: hip_ops.token_merge(cres[g][0].view(ndir, Bsz, L, Din), out=dxz[g][..., :Din]))
-        out = [dxz[0], dxz[1], None, None, None]
-        per = lambda f: [f(0), f(1)]
-        out += per(lambda g: cres[g][1].to(cw[g].dtype).reshape(cw[g].shape))
-        out += per(lambda g: cres[g][2].to(cb[g].dtype) if cb[g] is not None else None)
-        out += per(lambda g: dWx[g] if dWx[g].dtype == wx_dt else dWx[g].to(wx_dt))
-        out += per(lambda g: dWdt[g] if dWdt[g].dtype == wdt_dt else dWdt[g].to(wdt_dt))
-        out += per(lambda g: res[g][7].to(bias[g].dtype))
-        out += per(lambda g: res[g][5].to(A[g].dtype))
-        out += per(lambda g: res[g][6].to(Dk[g].dtype))
-        return tuple(out)
+            merged_dx = False
+            if _inner_on_own(G, M, dx_dbl[0], Wx_c[0], True, False):
+                _own_pair(dx_dbl, Wx_c, True, False, du.view(G, M, Din), accumulate=True)    # d x~ = du + dx_dbl @ Wx, in place, one launch
+            else:
+                for g in each:      # in place: an out-of-place addmm first copies `du` into its result (a 2 x 308 MB device memcpy per call)
+                    GemmChain.run(du[g].view(M, Din).addmm_, dx_dbl[g], Wx_c[g])
+            cres = stage(lambda g: hip_ops.gather_conv1d_bwd(xz[g][..., :Din], cw[g], cb[g], du[g], row_index=idx[g], ndir=ndir, silu=True))
+        if not merged_dx:                                          # K4x already summed the directions into dxz[..., :Din]
+            stage(lambda g: hip_ops.token_merge(cres[g][0].view(ndir, Bsz, L, Din), out=dxz[g][..., :Din]))
+        if not hoist:
+            stage(lambda g: hip_ops.token_merge(res[g][2].view(ndir, Bsz, L, Din), out=dxz[g][..., Din:]))
+        grads = (dxz, (None,) * G,
+                 [cres[g][1].to(cw[g].dtype).reshape(cw[g].shape) for g in each],
+                 [cres[g][2].to(cb[g].dtype) if cb[g] is not None else None for g in each],
+                 [t.to(wx_dt) for t in dWx], [t.to(wdt_dt) for t in dWdt],
+                 [res[g][7].to(bias[g].dtype) for g in each], [res[g][5].to(A[g].dtype) for g in each],
+                 [res[g][6].to(Dk[g].dtype) for g in each])
+        return (None, None, None, None) + tuple(t for field in grads for t in field)
 
 
 def spiral_ssm_pair_supported(Bsz, L, dtype, mix0, mix1):
@@ -684,76 +627,17 @@ def spiral_ssm_pair_supported(Bsz, L, dtype, mix0, mix1):
 
 def spiral_ssm_pair(xz0, xz1, mix0, mix1, A0, A1):
     """The fused 3-direction operator (spiral_ssm) for the two mixers of a block in one set of launches."""
+    per = lambda f: (f(mix0), f(mix1))
     with torch.autocast(device_type="cuda", enabled=False):
-        return _SpiralSSMPairFn.apply(xz0, xz1, mix0.scan_index, mix1.scan_index, torch.is_grad_enabled(),
-                                      mix0.conv1d.weight, mix1.conv1d.weight, mix0.conv1d.bias, mix1.conv1d.bias,
-                                      mix0.x_proj.weight, mix1.x_proj.weight, mix0.dt_proj.weight, mix1.dt_proj.weight,
-                                      mix0.dt_proj.bias.float(), mix1.dt_proj.bias.float(), A0.float(), A1.float(),
-                                      mix0.D.float(), mix1.D.float())
+        return _SpiralSSMFn.apply(torch.is_grad_enabled(), None, True, 2, xz0, xz1, *per(lambda m: m.scan_index),
+                                  *per(lambda m: m.conv1d.weight), *per(lambda m: m.conv1d.bias), *per(lambda m: m.x_proj.weight),
+                                  *per(lambda m: m.dt_proj.weight), *per(lambda m: m.dt_proj.bias.float()), A0.float(), A1.float(),
+                                  *per(lambda m: m.D.float()))
 
 
 # ------------------------------------------------------------------------------------------------
-# Token-major building blocks with autograd (used by the Mamba-2 mixer)
+# Mamba-2 mixer
 # ------------------------------------------------------------------------------------------------
-class _GatherConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, scan_index):
-        out = hip_ops.gather_conv1d_fwd(x, weight, bias, row_index=scan_index, ndir=scan_index.shape[0], silu=True)
-        ctx.save_for_backward(x, weight, bias, scan_index)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, weight, bias, scan_index = ctx.saved_tensors
-        ndir = scan_index.shape[0]
-        Bsz, L, Dm = x.shape
-        dout = dout.contiguous()
-        if dout.dtype != x.dtype:
-            dout = dout.to(x.dtype)
-        dx_slabs, dw, db = hip_ops.gather_conv1d_bwd(x, weight, bias, dout, row_index=scan_index, ndir=ndir, silu=True)
-        dx = hip_ops.token_merge(dx_slabs.view(ndir, Bsz, L, Dm))
-        return dx, dw.to(weight.dtype).reshape(weight.shape), (db.to(bias.dtype) if bias is not None else None), None
-
-
-def gather_conv1d(x, conv_weight, conv_bias, scan_index):
-    """x [B, L, C] token-major view -> SiLU(causal conv) of the token-gathered sequences, [ndir*B, L, C]."""
-    with torch.autocast(device_type="cuda", enabled=False):
-        return _GatherConvFn.apply(x, conv_weight, conv_bias, scan_index)
-
-
-class _IndexedScanFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, delta, A, Bm, Cm, D, z, dt_bias, scan_index, Bsz, grad_on=True):
-        S, L, Dm = u.shape
-        N = A.shape[1]
-        need_grad = grad_on and any(ctx.needs_input_grad[:8])
-        ckpt = hip_ops.alloc_scan_ckpt(S, L, N, Dm, u.dtype, u.device) if need_grad else None
-        A = A.contiguous()
-        y = hip_ops.scan_fwd(u, delta, A, Bm, Cm, D, z, dt_bias, True, z_row_index=scan_index, out_row_index=scan_index,
-                             batch_per_dir=Bsz, ckpt=ckpt)
-        ctx.Bsz = Bsz
-        ctx.save_for_backward(u, delta, A, Bm, Cm, D, z, dt_bias, scan_index, ckpt)
-        return y.view(scan_index.shape[0], Bsz, L, Dm)
-
-    @staticmethod
-    def backward(ctx, dy):
-        u, delta, A, Bm, Cm, D, z, dt_bias, scan_index, ckpt = ctx.saved_tensors
-        ndir, Bsz = scan_index.shape[0], ctx.Bsz
-        S, L, Dm = u.shape
-        # dy is per direction here (the gated RMSNorm sits between the scan and the merge): the kernel gathers its rows through
-        # the same table as the forward's scatter, indexed by sequence instead of by batch (DM_FLAG_DOUT_PER_SEQ); z is
-        # gathered in the kernel and dz comes back per direction in token order, so the 3 slabs only need the merge sum.
-        dy = dy.reshape(S, L, Dm).contiguous()
-        if dy.dtype != u.dtype:
-            dy = dy.to(u.dtype)
-        du, ddelta, dzs, dB, dC, dA, dD, dbias = hip_ops.scan_bwd(u, delta, A, Bm, Cm, D, z, dt_bias, dy, ckpt, True,
-                                                                  z_row_index=scan_index, out_row_index=scan_index,
-                                                                  batch_per_dir=Bsz, dout_per_seq=True)
-        dz = hip_ops.token_merge(dzs.view(ndir, Bsz, L, Dm))
-        return (du, ddelta, dA.to(A.dtype), dB.to(Bm.dtype), dC.to(Cm.dtype), dD.to(D.dtype), dz.to(z.dtype), dbias.to(dt_bias.dtype),
-                None, None, None)
-
-
 class _SpiralSSDFn(torch.autograd.Function):
     """The Mamba-2 mixer between in_proj and out_proj as ONE autograd node: zxbcdt [B, L, 2*Din + 2N + H] (token-major
     in_proj output, column blocks [z | x | B | C | dt], block/mamba2.py:380-400) -> gated, RMS-normalised, merged y [B, L, Din].
@@ -780,7 +664,7 @@ class _SpiralSSDFn(torch.autograd.Function):
             out, rstd = _SpiralSSDFn._norm_merge(ydir, norm_w, eps, ndir, Bsz, L, Din)
             if need_grad:
                 ctx.ssd = True
-                ctx.save_for_backward(zxbcdt, conv_w, conv_b, xBC, A_h, D_h, dt_bias_h, ydir, rstd, norm_w, scan_index)
+                ctx.save_for_backward(zxbcdt, conv_w, conv_b, xBC, ydir, rstd, norm_w, scan_index, A_h, D_h, dt_bias_h)
                 ctx.meta = (Din, N, H, P, eps, dt_bias_h.dtype, A_h.dtype, D_h.dtype)
             return out
         # dt is produced per token and per head: gather its rows per direction, broadcast head -> channels
@@ -794,7 +678,7 @@ class _SpiralSSDFn(torch.autograd.Function):
         ydir = hip_ops.scan_fwd(x, delta, A, Bm, Cm, Dskip, z, dt_bias, True, z_row_index=scan_index, out_row_index=scan_index,
                                 batch_per_dir=Bsz, ckpt=ckpt, a_shared=True)     # token order, gated; one decay per head
         out, rstd = _SpiralSSDFn._norm_merge(ydir, norm_w, eps, ndir, Bsz, L, Din)
-        ctx.save_for_backward(zxbcdt, conv_w, conv_b, xBC, delta, A, Dskip, dt_bias, ckpt, ydir, rstd, norm_w, scan_index, scan_index_inv)
+        ctx.save_for_backward(zxbcdt, conv_w, conv_b, xBC, ydir, rstd, norm_w, scan_index, delta, A, Dskip, dt_bias, ckpt, scan_index_inv)
         ctx.meta = (Din, N, H, P, eps, dt_bias_h.dtype, A_h.dtype, D_h.dtype)
         return out
 
@@ -816,9 +700,7 @@ class _SpiralSSDFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        if ctx.ssd:
-            return _SpiralSSDFn._backward_matrix_pipe(ctx, dout)
-        zxbcdt, conv_w, conv_b, xBC, delta, A, Dskip, dt_bias, ckpt, ydir, rstd, norm_w, scan_index, scan_index_inv = ctx.saved_tensors
+        zxbcdt, conv_w, conv_b, xBC, ydir, rstd, norm_w, scan_index, *arm = ctx.saved_tensors
         Din, N, H, P, eps, bias_dt, A_dt, D_dt = ctx.meta
         Bsz, L, _ = zxbcdt.shape
         ndir = scan_index.shape[0]
@@ -829,57 +711,38 @@ class _SpiralSSDFn(torch.autograd.Function):
         dyd, dnorm_w = _SpiralSSDFn._norm_merge_bwd(ydir, norm_w, eps, rstd, dout, ndir, Bsz, L, Din)                # [ndir, B, L, Din]
         dxBC = torch.empty((S, L, Cx), dtype=dt_, device=zxbcdt.device)
         x, Bm, Cm = xBC[..., :Din], xBC[..., Din:Din + N], xBC[..., Din + N:]
-        _, ddelta, dzs, _, _, dA, dD, dbias = hip_ops.scan_bwd(
-            x, delta, A, Bm, Cm, Dskip, zxbcdt[..., :Din], dt_bias, dyd.view(S, L, Din), ckpt, True, z_row_index=scan_index,
-            out_row_index=scan_index, batch_per_dir=Bsz, dout_per_seq=True, du_out=dxBC[..., :Din], a_shared=True,
-            dbc_out=dxBC[..., Din:])                                             # dB | dC land in their xBC columns
+        # either arm fills dxBC and yields dz per direction, the d dt columns in token order and the per-head dA, dD, d dt_bias
+        if ctx.ssd:
+            A_h, D_h, dt_bias_h = arm
+            _, dzs, dbc, ddt, dad = hip_ops.ssd_bwd(
+                x, Bm, Cm, zxbcdt[..., Din + Cx:], zxbcdt[..., :Din], dyd.view(S, L, Din), A_h, D_h, dt_bias_h, z_row_index=scan_index,
+                out_row_index=scan_index, batch_per_dir=Bsz, dx_out=dxBC[..., :Din])
+            dxBC[..., Din:].copy_(dbc)                                                    # dB | dC (summed over the heads) in their xBC columns
+            ddt4 = ddt.view(ndir, Bsz, L, H)                                              # already in token order, raw-dt gradient: add the directions
+            ddt_tok = ddt4[0] if ndir == 1 else ddt4.sum(0)
+            dA_h, dD_h, dbias_h = dad
+        else:
+            delta, A, Dskip, dt_bias, ckpt, scan_index_inv = arm
+            _, ddelta, dzs, _, _, dA, dD, dbias = hip_ops.scan_bwd(
+                x, delta, A, Bm, Cm, Dskip, zxbcdt[..., :Din], dt_bias, dyd.view(S, L, Din), ckpt, True, z_row_index=scan_index,
+                out_row_index=scan_index, batch_per_dir=Bsz, dout_per_seq=True, du_out=dxBC[..., :Din], a_shared=True,
+                dbc_out=dxBC[..., Din:])                                             # dB | dC land in their xBC columns
+            # d(dt): sum the head's channels, put every direction back in token order (adjoint of the row gather), add the directions
+            # (a matrix-vector product: the generic inner-dimension reduction kernel takes 150 us for this shape, the GEMV 20)
+            ddt = torch.mv(ddelta.view(S * L * H, P), torch.ones(P, dtype=dt_, device=zxbcdt.device)).view(ndir, Bsz, L, H)
+            inv64 = scan_index_inv.long()
+            ddt_tok = ddt[0][:, inv64[0]].float()
+            for k in range(1, ndir):
+                ddt_tok = ddt_tok + ddt[k][:, inv64[k]].float()
+            dA_h, dD_h, dbias_h = dA.view(H, P * N).sum(-1), dD.view(H, P).sum(-1), dbias.view(H, P).sum(-1)
         dx_slabs, dconv_w, dconv_b = hip_ops.gather_conv1d_bwd(zxbcdt[..., Din:Din + Cx], conv_w, conv_b, dxBC, row_index=scan_index,
                                                                ndir=ndir, silu=True)                              # token order
         dzx = torch.empty_like(zxbcdt)
         hip_ops.token_merge(dzs.view(ndir, Bsz, L, Din), out=dzx[..., :Din])
         hip_ops.token_merge(dx_slabs.view(ndir, Bsz, L, Cx), out=dzx[..., Din:Din + Cx])
-        # d(dt): sum the head's channels, put every direction back in token order (adjoint of the row gather), add the directions
-        # (a matrix-vector product: the generic inner-dimension reduction kernel takes 150 us for this shape, the GEMV 20)
-        ddt = torch.mv(ddelta.view(S * L * H, P), torch.ones(P, dtype=dt_, device=zxbcdt.device)).view(ndir, Bsz, L, H)
-        inv64 = scan_index_inv.long()
-        ddt_tok = ddt[0][:, inv64[0]].float()
-        for k in range(1, ndir):
-            ddt_tok = ddt_tok + ddt[k][:, inv64[k]].float()
         dzx[..., Din + Cx:].copy_(ddt_tok)
-        dA_h = dA.view(H, P * N).sum(-1)
-        dD_h = dD.view(H, P).sum(-1)
-        dbias_h = dbias.view(H, P).sum(-1)
         return (dzx, dconv_w.to(conv_w.dtype).reshape(conv_w.shape), dconv_b.to(conv_b.dtype) if conv_b is not None else None,
                 dbias_h.to(bias_dt), dA_h.to(A_dt), dD_h.to(D_dt), None if dnorm_w is None else dnorm_w.to(norm_w.dtype), None, None, None, None, None, None)
-
-
-    @staticmethod
-    def _backward_matrix_pipe(ctx, dout):
-        zxbcdt, conv_w, conv_b, xBC, A_h, D_h, dt_bias_h, ydir, rstd, norm_w, scan_index = ctx.saved_tensors
-        Din, N, H, P, eps, bias_dt, A_dt, D_dt = ctx.meta
-        Bsz, L, _ = zxbcdt.shape
-        ndir = scan_index.shape[0]
-        S, Cx = ndir * Bsz, Din + 2 * N
-        dt_ = zxbcdt.dtype
-        if dout.dtype != dt_:
-            dout = dout.to(dt_)
-        dyd, dnorm_w = _SpiralSSDFn._norm_merge_bwd(ydir, norm_w, eps, rstd, dout, ndir, Bsz, L, Din)                # [ndir, B, L, Din]
-        dxBC = torch.empty((S, L, Cx), dtype=dt_, device=zxbcdt.device)
-        x, Bm, Cm = xBC[..., :Din], xBC[..., Din:Din + N], xBC[..., Din + N:]
-        _, dzs, dbc, ddt, dad = hip_ops.ssd_bwd(
-            x, Bm, Cm, zxbcdt[..., Din + Cx:], zxbcdt[..., :Din], dyd.view(S, L, Din), A_h, D_h, dt_bias_h, z_row_index=scan_index,
-            out_row_index=scan_index, batch_per_dir=Bsz, dx_out=dxBC[..., :Din])
-        dxBC[..., Din:].copy_(dbc)                                                    # dB | dC (summed over the heads) in their xBC columns
-        dx_slabs, dconv_w, dconv_b = hip_ops.gather_conv1d_bwd(zxbcdt[..., Din:Din + Cx], conv_w, conv_b, dxBC, row_index=scan_index,
-                                                               ndir=ndir, silu=True)                              # token order
-        dzx = torch.empty_like(zxbcdt)
-        hip_ops.token_merge(dzs.view(ndir, Bsz, L, Din), out=dzx[..., :Din])
-        hip_ops.token_merge(dx_slabs.view(ndir, Bsz, L, Cx), out=dzx[..., Din:Din + Cx])
-        ddt4 = ddt.view(ndir, Bsz, L, H)                                              # already in token order, raw-dt gradient: add the directions
-        ddt_tok = ddt4[0] if ndir == 1 else ddt4.sum(0)
-        dzx[..., Din + Cx:].copy_(ddt_tok)
-        return (dzx, dconv_w.to(conv_w.dtype).reshape(conv_w.shape), dconv_b.to(conv_b.dtype) if conv_b is not None else None,
-                dad[2].to(bias_dt), dad[0].to(A_dt), dad[1].to(D_dt), None if dnorm_w is None else dnorm_w.to(norm_w.dtype), None, None, None, None, None, None)
 
 
 def spiral_ssd(zxbcdt, conv_w, conv_b, dt_bias, A, D, norm_w, eps, scan_index, scan_index_inv, d_inner, d_state):
@@ -887,44 +750,6 @@ def spiral_ssd(zxbcdt, conv_w, conv_b, dt_bias, A, D, norm_w, eps, scan_index, s
     with torch.autocast(device_type="cuda", enabled=False):
         return _SpiralSSDFn.apply(zxbcdt, conv_w, conv_b, dt_bias, A, D, norm_w, eps, scan_index, scan_index_inv, d_inner, d_state,
                                   torch.is_grad_enabled())
-
-
-def indexed_scan(u, delta, A, Bm, Cm, D, z, dt_bias, scan_index, Bsz):
-    """Selective scan of ndir*B token-gathered sequences with the z gather and the inverse (merge) reindex folded in.
-    u, delta: [ndir*B, L, Dm]; Bm, Cm: [ndir*B, L, N] views; z: [B, L, Dm] (token order).  Returns the gated output
-    [ndir, B, L, Dm] with every direction already back in TOKEN order."""
-    with torch.autocast(device_type="cuda", enabled=False):
-        if delta.dtype != u.dtype:
-            delta = delta.to(u.dtype)
-        if z is None:
-            raise NotImplementedError("norm_before_gate=True (ungated scan) is not wired; DiffMa uses norm_before_gate=False")
-        return _IndexedScanFn.apply(u, delta.contiguous(), A.float(), Bm, Cm, D.float(), z, dt_bias.float(), scan_index, Bsz,
-                                    torch.is_grad_enabled())
-
-
-class _RmsMergeFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, slabs, weight, eps):
-        slabs = slabs.contiguous()
-        out, rstd = hip_ops.rmsnorm_merge_fwd(slabs, weight, eps)
-        ctx.save_for_backward(slabs, weight, rstd)
-        ctx.eps = eps
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        slabs, weight, rstd = ctx.saved_tensors
-        if dout.dtype != slabs.dtype:
-            dout = dout.to(slabs.dtype)
-        dy, dw = hip_ops.rmsnorm_merge_bwd(slabs, weight, ctx.eps, rstd, dout)
-        return dy, dw.to(weight.dtype), None
-
-
-def rmsnorm_merge(slabs, weight, eps):
-    """[K, B, L, C] gated scan outputs (token order) -> weight * sum_k RMSNorm(slab_k): the Mamba-2 gated RMSNorm
-    (norm_before_gate = False, block/mamba2.py:349) fused with the 3-way CrossMerge."""
-    with torch.autocast(device_type="cuda", enabled=False):
-        return _RmsMergeFn.apply(slabs, weight, eps)
 
 
 def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, chunk_size, initial_states=None,
@@ -967,8 +792,8 @@ def spiral_ssm(xz, conv_w, conv_b, x_proj_w, dt_proj_w, dt_proj_b, A, Dskip, sca
     out_index / merge: see _SpiralSSMFn.forward.  Returns y [B, L, Din] (or [ndir, B, L, Din]); the caller applies out_proj.
     """
     with torch.autocast(device_type="cuda", enabled=False):
-        return _SpiralSSMFn.apply(xz, conv_w, conv_b, x_proj_w, dt_proj_w, dt_proj_b.float(), A.float(), Dskip.float(),
-                                  scan_index, torch.is_grad_enabled(), out_index, merge)
+        return _SpiralSSMFn.apply(torch.is_grad_enabled(), out_index, merge, 1, xz, scan_index, conv_w, conv_b, x_proj_w, dt_proj_w,
+                                  dt_proj_b.float(), A.float(), Dskip.float())[0]
 
 
 _CONSTS = {}

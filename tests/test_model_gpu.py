@@ -1207,6 +1207,66 @@ def test_paired_mixers_equal_two_unpaired_mixers_and_halve_the_launches(gpu, mon
     assert n1 < n0 and (n0 - n1) >= 10, (n0, n1)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_spiral_pair_equals_two_single_operators_bit_for_bit_on_library_projections(gpu, monkeypatch, dtype):
+    """spiral_ssm_pair against spiral_ssm on each mixer alone, with the pair's inner projections on the library (PAIR_OWN_MAX_ROWS 0):
+    one operator body serves both, the kernels are bit-identical under the `_n` launches and the library products are the same calls,
+    so both outputs and every gradient are EQUAL, and the pair makes fewer C-ABI calls.  spiral(8): L = 64 is the smallest length on
+    the chunk-parallel scans; d_model 256 (Din 512, dt_rank 16) the smallest width dm_dtproj_bwd takes."""
+    from diffma_amd import _lib
+    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd.mamba import Mamba
+    from diffma_amd.tools import spiral
+
+    monkeypatch.setattr(ssi, "PAIR_OWN_MAX_ROWS", 0)
+    torch.manual_seed(7)
+    n, B, d_model = 8, 1, 256
+    orders, inverses = spiral(n)
+    mixers = [Mamba(d_model=d_model, d_state=16, token_list=orders[k], token_list_reversal=orders[k + 1], origina_list=inverses[k],
+                    origina_list_reversal=inverses[k + 1]).to(gpu) for k in (2, 4)]
+    with torch.no_grad():
+        for m in mixers:
+            m.D.add_(0.1 * torch.randn_like(m.D))
+    assert ssi.spiral_ssm_pair_supported(B, n * n, dtype, *mixers)
+    Din = mixers[0].d_inner
+    xz = [torch.randn(B, n * n, 2 * Din, device=gpu).to(dtype) for _ in mixers]
+    dy = [torch.randn(B, n * n, Din, device=gpu).to(dtype) for _ in mixers]
+    names = ("conv1d.weight", "conv1d.bias", "x_proj.weight", "dt_proj.weight", "dt_proj.bias", "D")
+
+    def run(pair):
+        for m in mixers:
+            for p in m.parameters():
+                p.grad = None
+        xin = [t.clone().requires_grad_(True) for t in xz]
+        A = [(-torch.exp(m.A_log.detach().float())).requires_grad_(True) for m in mixers]
+        counts = {"n": 0}
+        real_call, real_call_n = _lib.call, _lib.call_n
+        monkeypatch.setattr(_lib, "call", lambda name, a, st: (counts.__setitem__("n", counts["n"] + 1), real_call(name, a, st))[1])
+        monkeypatch.setattr(_lib, "call_n", lambda name, a, st: (counts.__setitem__("n", counts["n"] + 1), real_call_n(name, a, st))[1])
+        if pair:
+            y = ssi.spiral_ssm_pair(xin[0], xin[1], mixers[0], mixers[1], A[0], A[1])
+        else:
+            y = [ssi.spiral_ssm(x, m.conv1d.weight, m.conv1d.bias, m.x_proj.weight, m.dt_proj.weight, m.dt_proj.bias, a, m.D, m.scan_index)
+                 for x, m, a in zip(xin, mixers, A)]
+        torch.autograd.backward(list(y), dy)
+        torch.cuda.synchronize()
+        monkeypatch.setattr(_lib, "call", real_call)
+        monkeypatch.setattr(_lib, "call_n", real_call_n)
+        got = {}
+        for g, m in enumerate(mixers):
+            got[f"{g}.y"], got[f"{g}.dxz"], got[f"{g}.dA"] = y[g].detach().clone(), xin[g].grad.clone(), A[g].grad.clone()
+            params = dict(m.named_parameters())
+            got.update({f"{g}.{k}": params[k].grad.clone() for k in names})
+        return got, counts["n"]
+
+    single, n_single = run(False)
+    paired, n_paired = run(True)
+    assert single.keys() == paired.keys() and len(single) == 2 * 9
+    for k in single:
+        assert torch.equal(paired[k], single[k]), (k, rel_l2(paired[k].float().cpu(), single[k].float().cpu()))
+    assert n_paired < n_single, (n_paired, n_single)
+
+
 # bounds of the bench-dispatch end-to-end test = 2x the worst case measured on MI355X (profiles/r06_e2e_bench_dispatch_worst.json: output rel-L2
 # 3.9e-3; worst parameter gradient 2.04e-2 -- the bias of the fusion MLP's last layer of block 0, a sum over 34 496 bf16 rows)
 E2E_OUT_TOL, E2E_GRAD_TOL = 8e-3, 4e-2
