@@ -337,4 +337,23 @@ __device__ __forceinline__ float wave_sum_dpp(float x) {
 }
 #undef DM_DPP_ADD
 
+template <int CTRL>
+__device__ __forceinline__ float dpp(float x) {
+    return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xF, 0xF, true));
+}
+constexpr int DPP_QUAD_SWAP = 0xB1;     // [1,0,3,2]  lane ^ 1
+constexpr int DPP_QUAD_HALF = 0x4E;     // [2,3,0,1]  lane ^ 2
+constexpr int DPP_ROW_ROR = 0x120;      // + n : rotate right by n inside a 16-lane row
+constexpr int DPP_ROW_HALF_MIRROR = 0x141;   // lane i <-> 7 - i inside every 8 lanes of a row
+
+// sum over the SPLIT consecutive lanes that share a channel (every lane gets the total)
+template <int SPLIT>
+__device__ __forceinline__ float slice_sum(float x) {
+    static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4 || SPLIT == 8, "a channel's lanes sit inside 8 lanes of a row");
+    if (SPLIT >= 2) x += dpp<DPP_QUAD_SWAP>(x);
+    if (SPLIT >= 4) x += dpp<DPP_QUAD_HALF>(x);
+    if (SPLIT >= 8) x += dpp<DPP_ROW_HALF_MIRROR>(x);   // every lane of a quad holds the quad's total: the mirror lane sits in the other quad
+    return x;
+}
+
 }  // namespace dm

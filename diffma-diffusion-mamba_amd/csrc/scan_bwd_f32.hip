@@ -12,6 +12,8 @@ extern "C" int dm_scan_bwd_group_channels(int dstate) {
 #ifndef DM_FAST_BUILD
         case 8: return (WAVE / bwd_split<8>::value) * BWD_WAVES;
         case 32: return (WAVE / bwd_split<32>::value) * BWD_WAVES;
+        case 64: return (WAVE / bwd_split<64>::value) * BWD_WAVES;
+        case 128: return (WAVE / bwd_split<128>::value) * BWD_WAVES;
 #endif
         default: return -1;
     }

@@ -5,7 +5,12 @@
 // path, reference train.py:259).  Equations: SURVEY.md A.1-bwd.
 //
 // Layout: token-major like the forward.  A lane owns SPLIT-th of a channel's states: for d_state 16 a whole channel
-// (SPLIT = 1, 64 channels per wave, 232 VGPRs, 2 waves/SIMD), for d_state 32 half of one (SPLIT = 2).  With the
+// (SPLIT = 1, 64 channels per wave, 232 VGPRs, 2 waves/SIMD), for d_state 32 half of one (SPLIT = 2), for d_state 64 a quarter
+// (SPLIT = 4) and for d_state 128 an eighth (SPLIT = 8): 16 states per lane from d_state 32 on.  A workgroup of 4 waves therefore
+// covers GC = 256 / SPLIT channels: 256 at d_state 8 / 16, 128 at 32, 64 at 64, 32 at 128 (dm_scan_bwd_group_channels).
+// Workspace: dBC_partial is [S][L][ceil(Dm / GC)][2 N] fp32 = S * L * ceil(Dm / GC) * 8 N bytes -- one row of 2 N sums per
+// (sequence, step, workgroup).  With GC = 4096 / N from d_state 32 on it grows with N^2 at fixed Dm: per (sequence, step) at
+// Dm = 1024 that is 0.5 KB at d_state 16, 2 KB at 32, 8 KB at 64 and 32 KB at 128.  With the
 // forward's checkpoints every 4 steps only 4 recomputed states per lane are live (64 VGPRs for 16 states); the earlier
 // 8-step scheme needed ~270 VGPRs for a whole channel and therefore ran 2 lanes per channel, which replicated every
 // per-channel instruction (softplus, silu', conversions, stores: a third of the issue slots) -- a whole channel per
@@ -95,7 +100,10 @@ template <typename T, typename TBC, int N, int SPLIT, bool HAS_Z, bool IDX, int 
 __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(N <= 16 ? 2 : 1))) void scan_bwd_kernel(const dm_scan_bwd_args p) {
     constexpr int NS = N / SPLIT, NPL = NS / 2, CW = WAVE / SPLIT, CK = BWD_CK, SUB = DM_SCAN_CKPT_EVERY, M = 2 * NS, R = M / 4;
     constexpr int ES = (int)sizeof(T);
-    constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value && M % 16 == 0;   // dB/dC lane-group sums on the matrix pipe
+    // dB/dC lane-group sums on the matrix pipe: bf16 I/O up to two lanes per channel.  d_state 64 / 128 (4 / 8 lanes per channel) take
+    // the exact permlane path in every dtype: built with the matrix-pipe form, their launches with row-index tables returned wrong
+    // gradients (NaN among them) on the device while the plain launches passed; the cause is not found, the form is not instantiated.
+    constexpr bool MFMA_RED = std::is_same<T, bf16_t>::value && M % 16 == 0 && SPLIT <= 2;
     // HALVES: the lane's 16 states as two groups of 8 walked one after the other, the recomputed steps' decay factors reused by the sweep
     constexpr bool HALVES = MFMA_RED && SPLIT == 1 && N == 16;
     constexpr int NH = HALVES ? 2 : 1, NPH = NPL / NH;
@@ -519,15 +527,16 @@ __global__ __launch_bounds__(64 * BWD_WAVES) __attribute__((amdgpu_waves_per_eu(
 }
 
 // lanes per channel: a whole channel per lane up to d_state 16 (two lanes per channel = 3 waves per SIMD measured +10 % at d_state 16,
-// profiles/r03_k2_experiments.txt), half of one at d_state 32
-template <int N> struct bwd_split { static constexpr int value = N >= 32 ? 2 : 1; };
+// profiles/r03_k2_experiments.txt), half of one at d_state 32; d_state 64 and 128 keep d_state 32's 16 states per lane (4 and 8 lanes
+// per channel: the register footprint, the LDS slots of the dB/dC reduction and the flush mapping are those of d_state 32)
+template <int N> struct bwd_split { static constexpr int value = N >= 32 ? (N >= 64 ? N / 16 : 2) : 1; };
 
 // The one rule for which (DMODE, ASH) instantiation a launch takes, for K2 and K2c alike: calls
 // f(std::integral_constant<int, DMODE>, std::bool_constant<ASH>).  The special forms are built for their call pattern only.
 template <int N, bool HAS_Z, bool IDX, typename F>
 static void with_bwd_variant(int flags, F f) {
     const bool sp = (flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
-    if constexpr (N == 16 && HAS_Z && IDX) {          // the one-exp variant: the Mamba-2 call pattern
+    if constexpr ((N == 16 || N == 64 || N == 128) && HAS_Z && IDX) {          // the one-exp variant: the Mamba-2 call pattern
         if ((flags & DM_FLAG_A_SHARED) && sp) return f(std::integral_constant<int, 1>{}, std::true_type{});
     }
     if constexpr (N == 16 && !HAS_Z && IDX) {         // the hoisted-gate / hoisted-softplus call pattern of the DiffMa mixer
@@ -556,8 +565,10 @@ static int bwd_dispatch_n(const dm_scan_bwd_args& a, hipStream_t st) {
 #ifndef DM_FAST_BUILD
         case 8: return launch_bwd<T, TBC, 8>(a, st);
         case 32: return launch_bwd<T, TBC, 32>(a, st);
+        case 64: return launch_bwd<T, TBC, 64>(a, st);
+        case 128: return launch_bwd<T, TBC, 128>(a, st);
 #endif
-        default: set_error("dm_selective_scan_bwd: d_state=%d not instantiated (8,16,32)", a.dstate); return DM_ERR_DSTATE;
+        default: set_error("dm_selective_scan_bwd: d_state=%d not instantiated (8,16,32,64,128)", a.dstate); return DM_ERR_DSTATE;
     }
 }
 

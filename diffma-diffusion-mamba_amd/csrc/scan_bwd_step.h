@@ -98,21 +98,7 @@ __device__ __forceinline__ float gate_gy(float g, float z, float& sz) {
     return g * z * sz;
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), CTRL, 0xF, 0xF, true));
-}
-constexpr int DPP_QUAD_SWAP = 0xB1;     // [1,0,3,2]  lane ^ 1
-constexpr int DPP_QUAD_HALF = 0x4E;     // [2,3,0,1]  lane ^ 2
-constexpr int DPP_ROW_ROR = 0x120;      // + n : rotate right by n inside a 16-lane row
-
-// sum over the SPLIT consecutive lanes that share a channel (every lane gets the total)
-template <int SPLIT>
-__device__ __forceinline__ float slice_sum(float x) {
-    if (SPLIT >= 2) x += dpp<DPP_QUAD_SWAP>(x);
-    if (SPLIT >= 4) x += dpp<DPP_QUAD_HALF>(x);
-    return x;
-}
+// (dpp<>, slice_sum<SPLIT>: dm_common.h -- the forward splits wide channels over lanes the same way)
 
 // the lane's sums over its states (yp2: C.h, GB2: lambda.B, dlA2: A2.Gt, one f32x2 of partial sums each) turned into the step's
 // outputs.  The lane that owns the channel adds dDi to its dD sum and ddl to its dbias sum.

@@ -8,6 +8,11 @@
 //   * token-major tensors [seq][l][d]: ONE LANE PER CHANNEL, one wave64 per 64 channels of one
 //     sequence.  Every per-step access of the wave is a single coalesced 256-B row segment, so there
 //     is no LDS transposition and no cross-lane traffic at all.
+//     (d_state 128: a whole channel per lane -- 128 registers of state and 128 of A2 next to the prefetch ring -- does not build
+//     without scratch, so a channel is split over fwd_split<128> = 4 consecutive lanes of 32 states each, 16 channels per wave
+//     (the one-exp form at d_state 64: 2 lanes, 32 channels per wave), as
+//     the backward splits its channels: the lanes of a channel load the same u / delta / z, meet once per step in two DPP adds for
+//     y, and all store the same y to the same address; checkpoints and last_state are written per slice.)
 //   * the recurrence runs sequentially in time inside the lane with the d_state states held in
 //     registers (packed f32x2 -> v_pk_mul/v_pk_fma): per (b,d,l) element that is N exp2 + ~2.5N packed
 //     VALU ops, i.e. the work-optimal count -- a wave-parallel associative (Blelloch) scan of the same
@@ -32,7 +37,8 @@ namespace dm {
 
 // One time step of the recurrence for one lane.
 // ASH (DM_FLAG_A_SHARED): every state of the channel decays with the same factor -> one exp per step.
-template <int N, bool HAS_Z, bool SOFTPLUS, bool ASH = false>
+// N counts the lane's states; SPLIT > 1: they are one of SPLIT slices of the channel, whose C.h sums meet here (slice_sum).
+template <int N, bool HAS_Z, bool SOFTPLUS, bool ASH = false, int SPLIT = 1>
 __device__ __forceinline__ float scan_step(f32x2 (&h)[N / 2], const f32x2 (&A2)[N / 2], const float (&Bv)[N],
                                            const float (&Cv)[N], float uu, float draw, float zz, float Dv, float bias) {
     float dl = draw + bias;
@@ -59,10 +65,16 @@ __device__ __forceinline__ float scan_step(f32x2 (&h)[N / 2], const f32x2 (&A2)[
         h[k] = a * h[k] + bb * du;
         acc += h[k] * cc;
     }
-    float y = acc.x + acc.y + Dv * uu;
+    float y;
+    if constexpr (SPLIT > 1) y = slice_sum<SPLIT>(acc.x + acc.y) + Dv * uu;
+    else y = acc.x + acc.y + Dv * uu;
     if (HAS_Z) y *= silu_f(zz);
     return y;
 }
+
+// lanes per channel (see the header): the widths up to 64 keep a whole channel per lane.  (The one-exp form at d_state 64 with fp32
+// checkpoints left a 640-byte private array in scratch as a whole channel per lane: it runs as two slices of 32 states.)
+template <int N, bool ASH = false> struct fwd_split { static constexpr int value = N >= 128 ? N / 32 : ((N == 64 && ASH) ? 2 : 1); };
 
 // IDX : z_row_index / out_row_index tables are used (both non-null)
 // CKPT: the state is written to p.ckpt after every DM_SCAN_CKPT_EVERY = 4 steps (fp32, or bf16 pairs for bf16 I/O)
@@ -75,7 +87,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     static_assert(!ACC || IDX, "accumulating launches are built for the model's call pattern (row-index tables)");
     static_assert(N % 2 == 0, "d_state must be even");
     static_assert(PF == 8, "the B/C staging below maps 8 steps onto the 64 lanes");
-    constexpr int NP = N / 2;
+    constexpr int FS = fwd_split<N, ASH>::value, NS = N / FS, CW = WAVE / FS;      // lanes per channel, states per lane, channels per wave
+    constexpr int NP = NS / 2;
+    static_assert(FS == 1 || (N % FS == 0 && NS % 8 == 0), "a slice is whole 16-byte groups of the packed checkpoints");
     constexpr int ES = (int)sizeof(T), EBC = (int)sizeof(TBC);
     // B_l / C_l rows are shared by every channel of a sequence.  The wave fetches the rows of a whole
     // block of PF steps with ONE vector load per lane (lane = step*8 + part; N/4 consecutive values each),
@@ -83,14 +97,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     // with broadcast ds_read_b128.  Nothing here is wave-shared, so no barrier is needed.
     constexpr int PER = N / 4;                       // B/C values fetched per lane per block
     __shared__ __attribute__((aligned(16))) float bc_lds[2][PF][2 * N];
-    const int d_raw = blockIdx.x * WAVE + threadIdx.x;
+    const int q = FS > 1 ? (int)threadIdx.x % FS : 0;                    // the lane's slice of its channel: states q*NS ..
+    const int d_raw = FS > 1 ? blockIdx.x * CW + (int)threadIdx.x / FS : blockIdx.x * WAVE + threadIdx.x;
     // Lanes past the last channel shadow channel dim-1: they help fetching B/C and then compute and store
     // exactly the same values to exactly the same addresses as that lane (a benign duplicate store), which
     // keeps every store unpredicated.
     const int d = (d_raw < p.dim) ? d_raw : p.dim - 1;
     const int L = p.seqlen;
     const int bpd = (p.batch_per_dir > 0) ? p.batch_per_dir : p.nseq;
-    const int grp = (blockIdx.x * WAVE) / (p.dim / p.ngroups);
+    const int grp = (blockIdx.x * CW) / (p.dim / p.ngroups);
     const int s = blockIdx.y;
     const int dir = s / bpd;
     const int sb = s - dir * bpd;
@@ -122,8 +137,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     f32x2 A2[NP];
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        A2[j].x = p.A[(int64_t)d * N + 2 * j] * LOG2E;
-        A2[j].y = p.A[(int64_t)d * N + 2 * j + 1] * LOG2E;
+        A2[j].x = p.A[(int64_t)d * N + q * NS + 2 * j] * LOG2E;
+        A2[j].y = p.A[(int64_t)d * N + q * NS + 2 * j + 1] * LOG2E;
     }
     const float Dv = p.D ? p.D[d] : 0.0f;
     const float bias = p.delta_bias ? p.delta_bias[d] : 0.0f;
@@ -133,7 +148,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     for (int j = 0; j < NP; ++j) h[j] = (f32x2){0.0f, 0.0f};
 
     constexpr bool CK_PACKED = std::is_same<T, bf16_t>::value;      // checkpoint = pairs of bf16 in one 32-bit word
-    constexpr int CK_ROWS = CK_PACKED ? NP : N;                     // 32-bit rows of [dim] per checkpoint
+    constexpr int CK_ROWS = CK_PACKED ? N / 2 : N;                  // 32-bit rows of [dim] per checkpoint
     const int nchunk = CKPT ? (L + DM_SCAN_CKPT_EVERY - 1) / DM_SCAN_CKPT_EVERY : 0;
     const rsrc_t r_ck = make_rsrc(CKPT ? (const uint32_t*)p.ckpt + (int64_t)s * nchunk * CK_ROWS * p.dim : nullptr);
     auto store_slot = [&](int c) {
@@ -141,12 +156,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
             uint32_t w[NP];
 #pragma unroll
             for (int k = 0; k < NP; ++k) asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w[k]) : "v"(h[k].x), "v"(h[k].y));
-            bio_st_words<NP>(w, r_ck, d * 16, c * p.dim * NP * 4, p.dim * 16);
+            // (the slice's place inside a checkpoint differs per lane: it rides in the VGPR part of the address)
+            bio_st_words<NP>(w, r_ck, FS > 1 ? d * 16 + q * (NS / 8) * p.dim * 16 : d * 16, c * p.dim * (N / 2) * 4, p.dim * 16);
         } else {
 #pragma unroll
             for (int k = 0; k < NP; ++k) {
-                bio<float>::st(r_ck, d * 4, ((c * N + 2 * k) * p.dim) * 4, h[k].x);
-                bio<float>::st(r_ck, d * 4, ((c * N + 2 * k + 1) * p.dim) * 4, h[k].y);
+                bio<float>::st(r_ck, FS > 1 ? (d + q * NS * p.dim) * 4 : d * 4, ((c * N + 2 * k) * p.dim) * 4, h[k].x);
+                bio<float>::st(r_ck, FS > 1 ? (d + q * NS * p.dim) * 4 : d * 4, ((c * N + 2 * k + 1) * p.dim) * 4, h[k].y);
             }
         }
     };
@@ -172,7 +188,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     auto fetch_bc = [&](int l0, float(&v)[PER]) {        // rows l0 .. l0+PF-1 (clamped), this lane's piece
         int l = l0 + bc_step;
         l = (l < L) ? l : L - 1;
-        bio_ld_vec<TBC, PER>(v, r_bc, vo_bc + l * sl_bc, 0);
+        if constexpr (N >= 128) {                         // 64 or 128 bytes per lane: as 16-byte loads
+            constexpr int E16 = 16 / EBC;
+#pragma unroll
+            for (int k = 0; k < PER / E16; ++k) {
+                float t[E16];
+                bio_ld_vec<TBC, E16>(t, r_bc, vo_bc + l * sl_bc + 16 * k, 0);
+#pragma unroll
+                for (int e = 0; e < E16; ++e) v[k * E16 + e] = t[e];
+            }
+        } else {
+            bio_ld_vec<TBC, PER>(v, r_bc, vo_bc + l * sl_bc, 0);
+        }
     };
     auto stash_bc = [&](int b, const float(&v)[PER]) {
 #pragma unroll
@@ -204,13 +231,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
 #pragma unroll
         for (int j = 0; j < PF; ++j) {
             const int l = l0 + j;
-            float Bc[N], Cc[N];
+            float Bc[NS], Cc[NS];
 #pragma unroll
-            for (int k = 0; k < N; ++k) {
-                Bc[k] = bc_lds[buf][j][k];
-                Cc[k] = bc_lds[buf][j][N + k];
+            for (int k = 0; k < NS; ++k) {
+                Bc[k] = bc_lds[buf][j][q * NS + k];
+                Cc[k] = bc_lds[buf][j][N + q * NS + k];
             }
-            float y = scan_step<N, HAS_Z, SOFTPLUS, ASH>(h, A2, Bc, Cc, cu[j], cd[j], HAS_Z ? cz[j] : 0.0f, Dv, bias);
+            float y = scan_step<NS, HAS_Z, SOFTPLUS, ASH, FS>(h, A2, Bc, Cc, cu[j], cd[j], HAS_Z ? cz[j] : 0.0f, Dv, bias);
             if (ACC) y += co[j];
             bio<T>::st(r_o, vo, (IDX ? oidx[l] : l) * sl_o, y);
             if (CKPT && (j + 1) % DM_SCAN_CKPT_EVERY == 0) store_ckpt(l0 + j + 1);      // l0 is a multiple of PF
@@ -241,13 +268,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     for (int j = 0; j < PF; ++j) {
         const int l = Lfull + j;
         if (l < L) {
-            float Bc[N], Cc[N];
+            float Bc[NS], Cc[NS];
 #pragma unroll
-            for (int k = 0; k < N; ++k) {
-                Bc[k] = bc_lds[buf][j][k];
-                Cc[k] = bc_lds[buf][j][N + k];
+            for (int k = 0; k < NS; ++k) {
+                Bc[k] = bc_lds[buf][j][q * NS + k];
+                Cc[k] = bc_lds[buf][j][N + q * NS + k];
             }
-            float y = scan_step<N, HAS_Z, SOFTPLUS, ASH>(h, A2, Bc, Cc, ru[j], rd[j], HAS_Z ? rz[j] : 0.0f, Dv, bias);
+            float y = scan_step<NS, HAS_Z, SOFTPLUS, ASH, FS>(h, A2, Bc, Cc, ru[j], rd[j], HAS_Z ? rz[j] : 0.0f, Dv, bias);
             if (ACC) y += ro[j];
             bio<T>::st(r_o, vo, (IDX ? oidx[l] : l) * sl_o, y);
             if (CKPT && (j + 1) % DM_SCAN_CKPT_EVERY == 0) store_ckpt(l + 1);
@@ -257,7 +284,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
     if (CKPT) store_slot(0);                   // slot 0 (chunk 0 starts from zero) holds the state after the last step
 
     if (p.last_state) {
-        float* ls = p.last_state + ((int64_t)s * N) * p.dim + d;
+        float* ls = p.last_state + ((int64_t)s * N + q * NS) * p.dim + d;
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             ls[(int64_t)(2 * k) * p.dim] = h[k].x;
@@ -270,8 +297,10 @@ constexpr int SCAN_PF = 8;
 static_assert(SCAN_PF % DM_SCAN_CKPT_EVERY == 0, "checkpoints fall on fixed positions of a prefetch block");
 
 template <typename T, typename TBC, int N, bool HAS_Z, bool IDX>
-static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st, dim3 grid) {
+static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st) {
     const bool sp = (a.flags & DM_FLAG_DELTA_SOFTPLUS) != 0;
+    constexpr int CW = WAVE / fwd_split<N>::value;      // channels per wave
+    const dim3 grid((a.dim + CW - 1) / CW, a.nseq);
     if constexpr (N == 16 && HAS_Z && IDX) {          // accumulating launch: the model's call pattern only
         if ((a.flags & DM_FLAG_OUT_ACCUMULATE) && sp && !(a.flags & DM_FLAG_A_SHARED)) {
             if (a.ckpt) hipLaunchKernelGGL((scan_fwd_kernel<T, TBC, N, true, true, true, true, SCAN_PF, false, true>), grid, dim3(WAVE), 0, st, a);
@@ -279,10 +308,12 @@ static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st, dim3 grid) {
             return;
         }
     }
-    if constexpr (N == 16 && HAS_Z && IDX) {          // the one-exp variant is built for the Mamba-2 call pattern only
+    if constexpr ((N == 16 || N == 64 || N == 128) && HAS_Z && IDX) {          // the one-exp variant is built for the Mamba-2 call pattern only (its d_state: 16 on the scan pair, 64, 128)
         if ((a.flags & DM_FLAG_A_SHARED) && sp) {
-            if (a.ckpt) hipLaunchKernelGGL((scan_fwd_kernel<T, TBC, N, true, true, true, true, SCAN_PF, true>), grid, dim3(WAVE), 0, st, a);
-            else hipLaunchKernelGGL((scan_fwd_kernel<T, TBC, N, true, true, false, true, SCAN_PF, true>), grid, dim3(WAVE), 0, st, a);
+            constexpr int CWA = WAVE / fwd_split<N, true>::value;
+            const dim3 grid_a((a.dim + CWA - 1) / CWA, a.nseq);
+            if (a.ckpt) hipLaunchKernelGGL((scan_fwd_kernel<T, TBC, N, true, true, true, true, SCAN_PF, true>), grid_a, dim3(WAVE), 0, st, a);
+            else hipLaunchKernelGGL((scan_fwd_kernel<T, TBC, N, true, true, false, true, SCAN_PF, true>), grid_a, dim3(WAVE), 0, st, a);
             return;
         }
     }
@@ -297,8 +328,7 @@ static void launch_fwd3(const dm_scan_fwd_args& a, hipStream_t st, dim3 grid) {
 
 template <typename T, typename TBC, int N>
 static int launch_fwd(const dm_scan_fwd_args& a, hipStream_t st) {
-    dim3 grid((a.dim + WAVE - 1) / WAVE, a.nseq);
-    with_z_idx(a, [&](auto hz, auto ix) { launch_fwd3<T, TBC, N, hz.value, ix.value>(a, st, grid); });
+    with_z_idx(a, [&](auto hz, auto ix) { launch_fwd3<T, TBC, N, hz.value, ix.value>(a, st); });
     return launch_status("dm_selective_scan_fwd");
 }
 
@@ -310,9 +340,10 @@ static int dispatch_n(const dm_scan_fwd_args& a, hipStream_t st) {
         case 8: return launch_fwd<T, TBC, 8>(a, st);
         case 32: return launch_fwd<T, TBC, 32>(a, st);
         case 64: return launch_fwd<T, TBC, 64>(a, st);
+        case 128: return launch_fwd<T, TBC, 128>(a, st);
 #endif
         default:
-            set_error("dm_selective_scan_fwd: d_state=%d not instantiated (8,16,32,64)", a.dstate);
+            set_error("dm_selective_scan_fwd: d_state=%d not instantiated (8,16,32,64,128)", a.dstate);
             return DM_ERR_DSTATE;
     }
 }

@@ -321,6 +321,16 @@ def _scan_fwd_launch(u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, z_ro
     return out
 
 
+def scan_bwd_partial_shape(S, L, Dm, N, flags=0):
+    """Shape [S, L, ceil(Dm / GC), 2N] of the fp32 dB/dC partial rows that scan_bwd allocates (shapes only, no device).  GC =
+    dm_scan_bwd_launch_group_channels: 64 for the chunk-parallel kernel, else 256 up to d_state 16 and 4096 / N from d_state 32
+    on -- at a fixed Dm the buffer grows with N^2 (include/diffma_hip.h, dm_scan_bwd_args)."""
+    gc = _lib.load().dm_scan_bwd_launch_group_channels(S, Dm, L, N, flags)
+    if gc <= 0:
+        raise _lib.DiffmaHipError(f"selective-scan backward is not built for d_state={N}")
+    return (S, L, (Dm + gc - 1) // gc, 2 * N)
+
+
 def scan_bwd(u, delta, A, Bm, Cm, D, z, delta_bias, dout, ckpt, delta_softplus=True, *,
              z_row_index=None, out_row_index=None, batch_per_dir=0, ckpt_every=SCAN_CKPT_EVERY,
              ngroups=1, dz_out=None, dout_per_seq=False, du_out=None, a_shared=False, dbc_out=None, variant=None,
@@ -335,17 +345,15 @@ def scan_bwd(u, delta, A, Bm, Cm, D, z, delta_bias, dout, ckpt, delta_softplus=T
     A32, D32, b32 = _f32c(A), _f32c(D), _f32c(delta_bias)
     a = _scan_args(dm_scan_bwd_args(), u, delta, A32, Bm, Cm, D32, z, b32, delta_softplus, delta_activated, z_row_index, out_row_index,
                    batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, variant, DM_FLAG_DOUT_PER_SEQ if dout_per_seq else 0)
-    gc = _lib.load().dm_scan_bwd_launch_group_channels(S, Dm, L, N, a.flags)   # 256 (sequential kernel) or 64 (chunk-parallel, small launches)
-    if gc <= 0:
-        raise _lib.DiffmaHipError(f"selective-scan backward is not built for d_state={N}")
-    nw = (Dm + gc - 1) // gc
+    dbc_shape = scan_bwd_partial_shape(S, L, Dm, N, a.flags)   # a row per 256 / SPLIT channels (sequential kernel) or per 64 (chunk-parallel, small launches)
+    nw = dbc_shape[2]
     dev = u.device
     du = du_out if du_out is not None else torch.empty_like(u)      # du_out: a [S, L, Dm] view with channel stride 1
     ddelta = torch.empty((S, L, Dm), dtype=u.dtype, device=dev)
     dz = None
     if z is not None:
         dz = dz_out if dz_out is not None else torch.empty((S, L, Dm), dtype=u.dtype, device=dev)
-    dBC = torch.empty((S, L, nw, 2 * N), dtype=torch.float32, device=dev)
+    dBC = torch.empty(dbc_shape, dtype=torch.float32, device=dev)
     # per-sequence partial rows of dA | dD | dbias as column blocks of ONE buffer: one column sum instead of three
     want_dD, want_db = D is not None, (delta_bias is not None or delta_activated)
     pcols = Dm * N + Dm * (int(want_dD) + int(want_db))

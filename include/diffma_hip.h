@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 29
+#define DM_ABI_VERSION 30
 
 typedef enum {
     DM_OK = 0,
@@ -171,6 +171,13 @@ int dm_grads_nonfinite(const dm_adamw_args *args, void *stream);
  * instruction), state 2k in the low half and 2k+1 in the high half of word k (bf16 I/O: the recomputed states inherit
  * the precision the I/O tensors already have).  The buffer is private to the forward / backward pair of one build.
  * last_state (optional): final h, fp32, layout [s][n][d].
+ *
+ * d_state (ABI 30): instantiated for 8, 16, 32, 64 and 128 in every I/O dtype, with fp32 or I/O-dtype B/C, with and without z, row
+ * indices, checkpoints, last_state and DM_FLAG_DELTA_SOFTPLUS; anything else returns DM_ERR_DSTATE ("not instantiated
+ * (8,16,32,64,128)").  Up to 64 a lane owns a whole channel; at 128 a channel is split over 4 lanes (csrc/scan_fwd_impl.h).
+ * DM_FLAG_A_SHARED selects the one-exp form at d_state 16, 64 and 128 for the Mamba-2 call pattern (z, row indices,
+ * DM_FLAG_DELTA_SOFTPLUS); elsewhere the flag is accepted and the general form runs.  DM_FLAG_OUT_ACCUMULATE,
+ * DM_FLAG_DELTA_ACTIVATED and the chunk-parallel kernels are d_state 16 only.  A build with -DDM_FAST_BUILD has d_state 16 only.
  * ---------------------------------------------------------------------------------------------- */
 #define DM_SCAN_CKPT_EVERY 4 /* the one checkpoint spacing the kernels are built for = the backward's sub-chunk length; the value ckpt_every must hold */
 typedef struct {
@@ -214,6 +221,15 @@ int dm_selective_scan_fwd(const dm_scan_fwd_args *args, void *stream);
  *          [s][l][ceil(dim/GC)][2*dstate] (B then C);
  *   dA: [s][dim][dstate], dD: [s][dim], ddelta_bias: [s][dim]  fp32 per-sequence partials.
  *   The caller reduces the partials (deterministic; no atomics).
+ *
+ * d_state (ABI 30): instantiated for 8, 16, 32, 64 and 128 (the same dtype / z / row-index / delta-mode combinations at every
+ * width); anything else returns DM_ERR_DSTATE ("not instantiated (8,16,32,64,128)").  A lane owns 16 states from d_state 32 on,
+ * so GC = dm_scan_bwd_group_channels(dstate) is 256 at d_state 8 and 16, 128 at 32, 64 at 64 and 32 at 128, and
+ *   bytes(dBC_partial) = nseq * seqlen * ceil(dim / GC) * 2 * dstate * 4
+ * -- with GC = 4096 / dstate it grows with dstate^2 at a fixed dim: per (sequence, step) at dim 1024 it is 0.5 KB at d_state 16,
+ * 2 KB at 32, 8 KB at 64, 32 KB at 128.  DM_FLAG_A_SHARED selects the one-exp form at d_state 16, 64 and 128 for the Mamba-2
+ * call pattern (z, row indices, DM_FLAG_DELTA_SOFTPLUS; used with DM_FLAG_DOUT_PER_SEQ); DM_FLAG_DELTA_ACTIVATED and the
+ * chunk-parallel kernel are d_state 16 only.  A build with -DDM_FAST_BUILD has d_state 16 only.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t nseq, dim, seqlen, dstate;
