@@ -1177,30 +1177,48 @@ def training_loss_bwd(grad, g_eps, g_v, out_dtype):
 # element-wise exps; X / z / out tiles move as 16-byte row pieces through LDS.  DIFFMA_SSD_MFMA=0 returns the no-grad Mamba-2
 # mixer to the A-shared scan.  fp32 I/O stays on the scan; the backward twin is ssd_bwd below.
 SSD_MFMA = os.environ.get("DIFFMA_SSD_MFMA", "1") == "1"
+# The state widths the dispatch sends to dm_ssd_fwd by default: those at which it beats the A-shared scan by 1.1 x or more at all
+# three launch sizes.  A width the C ABI serves but this tuple leaves out stays reachable through ssd_fwd() itself.  At the wide
+# states (32, 64, 128) only the forward exists: no-grad calls (sampling, EMA evaluation) take it, training takes the A-shared scan
+# pair.  Same shape as above, dm_ssd_fwd vs scan in us at nseq 24 / 192 / 768 (profiles/ssd_fwd_wide.json, one MI355X, one session):
+#     d_state  32    32 vs 121    112 vs  281    402 vs  874      191 VGPRs,  69 KB LDS   } one 8-wave workgroup per (sequence, 4 heads),
+#     d_state  64    34 vs 122    123 vs  335    449 vs 1136      208 VGPRs,  97 KB LDS   } raw B / C rows staged in LDS: one workgroup
+#     d_state 128    38 vs 160    137 vs  872    500 vs 3264      228 VGPRs, 153 KB LDS   } per CU, 2 waves per SIMD
+# (d_state 16 in that session: 26 vs 65, 95 vs 148, 408 vs 432; its forward is within 2 % of the build before the wide kernel.)
+SSD_FWD_WIDTHS = (16, 32, 64, 128)
 
 
-def ssd_fwd_supported(x, L, headdim, dstate, views=()):
-    """views: the x / B / C / z views the launch would get -- their rows must start on 16-byte boundaries (tiles move as 16-byte pieces)."""
+def ssd_fwd_supported(x, L, headdim, dstate, views=(), gate=None):
+    """views: the x / B / C / z views the launch would get -- their rows must start on 16-byte boundaries (tiles move as 16-byte pieces).
+    gate: z passed apart from `views`; at the wide states its rows need 4-byte boundaries only (csrc/ssd.hip reads such a gate as dwords)."""
     if not (SSD_MFMA and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)):
+        return False
+    if int(dstate) not in SSD_FWD_WIDTHS:
         return False
     for v in views:
         if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
+            return False
+    if gate is not None:
+        unit, per = (16, 8) if int(dstate) == 16 else (4, 2)
+        if gate.data_ptr() % unit or gate.stride(-1) != 1 or any(st % per for st in gate.stride()[:-1]):
             return False
     return bool(_lib.load().dm_ssd_fwd_supported(int(L), int(headdim), int(dstate), dtype_code(x)))
 
 
 def ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_row_index=None, batch_per_dir=0, out=None):
-    """x: [S, L, H*64] view, Bm / Cm: [S, L, 16] views (after the conv, per gathered sequence); dt_tok: [B, L, H] and z: [B, L, H*64]
-    in token order; A_h, D_h, dt_bias_h: [H] fp32.  Returns the gated output [S, L, H*64] with step l at row out_row_index[dir][l]."""
+    """x: [S, L, H*64] view, Bm / Cm: [S, L, N] views, N = d_state in 16 / 32 / 64 / 128 (after the conv, per gathered sequence);
+    dt_tok: [B, L, H] and z: [B, L, H*64] in token order; A_h, D_h, dt_bias_h: [H] fp32.  Returns the gated output [S, L, H*64] with
+    step l at row out_row_index[dir][l]."""
     _require_gpu(x, Bm, Cm, dt_tok, z)
     S, L, Din = x.shape
     H = A_h.shape[0]
-    assert Din == H * 64 and Bm.shape[-1] == 16 and x.stride(2) == 1 and Bm.stride(2) == 1 and Cm.stride(2) == 1 and dt_tok.stride(2) == 1
+    N = Bm.shape[-1]
+    assert Din == H * 64 and Cm.shape[-1] == N and x.stride(2) == 1 and Bm.stride(2) == 1 and Cm.stride(2) == 1 and dt_tok.stride(2) == 1
     if out is None:
         out = torch.empty((S, L, Din), dtype=x.dtype, device=x.device)
     A32, D32, b32 = _f32c(A_h), _f32c(D_h), _f32c(dt_bias_h)
     a = dm_ssd_fwd_args()
-    a.nseq, a.batch_per_dir, a.seqlen, a.nheads, a.headdim, a.dstate = S, batch_per_dir, L, H, 64, 16
+    a.nseq, a.batch_per_dir, a.seqlen, a.nheads, a.headdim, a.dstate = S, batch_per_dir, L, H, 64, N
     a.io_dtype, a.flags = dtype_code(x), 0
     a.x, a.B, a.C, a.dt, a.z = _ptr(x), _ptr(Bm), _ptr(Cm), _ptr(dt_tok), _ptr(z)
     a.A, a.D, a.dt_bias = _ptr(A32), _ptr(D32), _ptr(b32)
@@ -1214,7 +1232,7 @@ def ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_
         a.z_ss, a.z_sl = z.stride(0), z.stride(1)
     a.o_ss, a.o_sl = out.stride(0), out.stride(1)
     es = x.element_size()
-    _launch("dm_ssd_fwd", a, x, (3 if z is not None else 2) * S * L * Din * es + 2 * S * L * 16 * es)
+    _launch("dm_ssd_fwd", a, x, (3 if z is not None else 2) * S * L * Din * es + 2 * S * L * N * es)
     return out
 
 

@@ -655,10 +655,11 @@ class _SpiralSSDFn(torch.autograd.Function):
         x, Bm, Cm = xBC[..., :Din], xBC[..., Din:Din + N], xBC[..., Din + N:]
         need_grad = grad_on and any(ctx.needs_input_grad[:7])
         ctx.ssd = False
-        if hip_ops.ssd_fwd_supported(xBC, L, P, N, views=(x, Bm, Cm, z)) and (not need_grad or hip_ops.ssd_bwd_supported(xBC, L, P, N)):
+        if hip_ops.ssd_fwd_supported(xBC, L, P, N, views=(x, Bm, Cm), gate=z) and (not need_grad or hip_ops.ssd_bwd_supported(xBC, L, P, N)):
             # the matrix pipe (csrc/ssd.hip, ssd_bwd.hip): single-chunk SSD as dense tile products per (sequence, head), the per-head
             # dt read in the kernel through the gather table -- no [S, L, Din] delta tensor, no per-state recurrence, and nothing
-            # but the operands saved for the backward (which recomputes the score tiles)
+            # but the operands saved for the backward (which recomputes the score tiles).  The backward exists at d_state 16 only:
+            # at the wide states of hip_ops.SSD_FWD_WIDTHS a no-grad call comes here, a call that needs gradients takes the scan pair
             ydir = hip_ops.ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index=scan_index, out_row_index=scan_index,
                                    batch_per_dir=Bsz)
             out, rstd = _SpiralSSDFn._norm_merge(ydir, norm_w, eps, ndir, Bsz, L, Din)
@@ -775,7 +776,8 @@ def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias
     if zxbcdt.stride(-1) != 1:
         zxbcdt = zxbcdt.contiguous()
     # ONE autograd node, the same one the Mamba2 module runs with three directions: conv (K3), the single-chunk SSD core on the
-    # matrix pipe (dm_ssd_fwd / dm_ssd_bwd) when the shape allows it -- 16-bit I/O, headdim 64, d_state 16, 16-byte aligned rows --
+    # matrix pipe (dm_ssd_fwd / dm_ssd_bwd) when the shape allows it -- 16-bit I/O, headdim 64, 16-byte aligned rows, d_state 16 (or,
+    # without gradients, a wide state of hip_ops.SSD_FWD_WIDTHS) --
     # else the A-shared selective scan, then the gated RMSNorm (dm_rmsnorm_merge_*, one slab) when rmsnorm_weight is given.
     ident = _const("ident", L, zxbcdt.device)
     y = spiral_ssd(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, rmsnorm_weight, rmsnorm_eps, ident, ident, dim, N)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 30
+#define DM_ABI_VERSION 31
 
 typedef enum {
     DM_OK = 0,
@@ -641,8 +641,14 @@ int dm_sum_partials(const dm_sum_partials_args *args, void *stream);
  *     y = (G diag(dt)) x + D[h] x;   out = y * silu(z)
  * x: [nseq][L][nheads*64] view (the conv output's x columns), B, C: [nseq][L][16] views (16-byte aligned rows), all after the
  * conv, per gathered sequence; dt_raw: [batch][L][nheads] and z: [batch][L][nheads*64] in TOKEN order, read through z_row_index;
- * out: [nseq][rows][nheads*64], step l stored at row out_row_index[dir][l].  16-bit I/O, headdim 64, d_state 16,
- * seqlen <= 224: dm_ssd_fwd_supported() tells; everything else takes the A-shared scan.  dm_ssd_bwd below is its backward.
+ * out: [nseq][rows][nheads*64], step l stored at row out_row_index[dir][l].  16-bit I/O, headdim 64, seqlen <= 224 and
+ * d_state 16, 32, 64 or 128 (B, C are then [nseq][L][dstate] views; at every width a row starts on a 16-byte boundary: base
+ * pointer 16-byte aligned, sequence and row strides multiples of 8 elements): dm_ssd_fwd_supported() tells; everything else
+ * takes the A-shared scan.  d_state 16 runs one wave per (sequence, head, half) with B in registers; the wide states run
+ * one 8-wave workgroup per (sequence, 4 heads) with the raw B / C rows staged in LDS (up to 153 KB of dynamic LDS).
+ * At the wide states the rows of z may start on 4-byte boundaries (the gate of a two-head mixer: in_proj rows of 2 Din + 2 N + 2).
+ * dm_ssd_bwd below is the backward at d_state 16 ONLY: at wide states the forward serves no-grad calls, training takes the
+ * A-shared scan pair.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t nseq, batch_per_dir, seqlen, nheads, headdim, dstate;

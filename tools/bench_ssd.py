@@ -1,11 +1,17 @@
-"""Mamba-2 SSD forward on the matrix pipe (K6) against the A-shared scan at the DiffMa-XL/2 --use-mamba2 shape -- run on the GPU box."""
-import os, sys, json
+"""Mamba-2 SSD forward on the matrix pipe (K6) against the A-shared scan at the DiffMa-XL/2 --use-mamba2 shape -- run on the GPU box.
+    tools/bench_ssd.py [--d-state N] [batch ...]      N in 16 (default) / 32 / 64 / 128; at the wide states only the forward pair
+is timed (the matrix-pipe backward is d_state 16 only)."""
+import argparse, os, sys, json
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffma_amd import hip_ops  # noqa: E402
 
 dev = torch.device("cuda", 0)
-L, H, P, N = 196, 16, 64, 16
+ap = argparse.ArgumentParser()
+ap.add_argument("--d-state", type=int, default=16)
+ap.add_argument("batches", nargs="*", type=int, default=[8, 64, 256])
+args = ap.parse_args()
+L, H, P, N = 196, 16, 64, args.d_state
 Din = H * P
 dt_ = torch.bfloat16
 
@@ -23,7 +29,7 @@ def timeit(fn, iters=int(os.environ.get("SSD_ITERS", "30"))):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-for B in [int(a) for a in (sys.argv[1:] or ["8", "64", "256"])]:
+for B in args.batches:
     S = 3 * B
     xBC = torch.randn(S, L, Din + 2 * N, device=dev).to(dt_)
     dt_tok = (torch.randn(B, L, H, device=dev) * 0.7 - 1.0).to(dt_)
@@ -45,26 +51,31 @@ for B in [int(a) for a in (sys.argv[1:] or ["8", "64", "256"])]:
         dtg = torch.stack([dt_tok[:, idx64[k]] for k in range(3)]).reshape(S, L, H, 1).expand(S, L, H, P).reshape(S, L, Din)
         return hip_ops.scan_fwd(x, dtg, A, Bm, Cm, Dp, z, bp, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, a_shared=True, out=out)
 
-    # ---- backward: K6b against the A-shared scan backward (which also needs the forward's checkpoints and the expanded delta) ----
-    dout = torch.randn(S, L, Din, device=dev).to(dt_)
-    dxBC = torch.empty_like(xBC)
+    def bench_bwd():
+        # ---- backward: K6b against the A-shared scan backward (which also needs the forward's checkpoints and the expanded delta) ----
+        dout = torch.randn(S, L, Din, device=dev).to(dt_)
+        dxBC = torch.empty_like(xBC)
 
-    def mfma_bwd():
-        return hip_ops.ssd_bwd(x, Bm, Cm, dt_tok, z, dout, A_h, D_h, b_h, z_row_index=idx, out_row_index=idx, batch_per_dir=B, dx_out=dxBC[..., :Din])
+        def mfma_bwd():
+            return hip_ops.ssd_bwd(x, Bm, Cm, dt_tok, z, dout, A_h, D_h, b_h, z_row_index=idx, out_row_index=idx, batch_per_dir=B, dx_out=dxBC[..., :Din])
 
-    dtg = torch.stack([dt_tok[:, idx64[k]] for k in range(3)]).reshape(S, L, H, 1).expand(S, L, H, P).reshape(S, L, Din)
-    ckpt = hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev)
-    hip_ops.scan_fwd(x, dtg, A, Bm, Cm, Dp, z, bp, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, a_shared=True, out=out, ckpt=ckpt)
+        dtg = torch.stack([dt_tok[:, idx64[k]] for k in range(3)]).reshape(S, L, H, 1).expand(S, L, H, P).reshape(S, L, Din)
+        ckpt = hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev)
+        hip_ops.scan_fwd(x, dtg, A, Bm, Cm, Dp, z, bp, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, a_shared=True, out=out, ckpt=ckpt)
 
-    def scan_bwd():
-        return hip_ops.scan_bwd(x, dtg, A, Bm, Cm, Dp, z, bp, dout, ckpt, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, dout_per_seq=True,
-                                du_out=dxBC[..., :Din], a_shared=True, dbc_out=dxBC[..., Din:])
+        def scan_bwd():
+            return hip_ops.scan_bwd(x, dtg, A, Bm, Cm, Dp, z, bp, dout, ckpt, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, dout_per_seq=True,
+                                    du_out=dxBC[..., :Din], a_shared=True, dbc_out=dxBC[..., Din:])
 
-    t_mb, t_sb = timeit(mfma_bwd), timeit(scan_bwd)
+        t_mb, t_sb = timeit(mfma_bwd), timeit(scan_bwd)
+        return dict(ssd_bwd_mfma_us=round(t_mb, 1), a_shared_scan_bwd_us=round(t_sb, 1))
+
     a = mfma().float().clone()
     b = scan().float()
     nb = 3 * S * L * Din * 2
     t_m, t_s = timeit(mfma), timeit(scan)
-    print(json.dumps(dict(batch=B, nseq=S, ssd_mfma_us=round(t_m, 1), a_shared_scan_us=round(t_s, 1), mfma_GBps=round(nb / t_m / 1e3, 1),
-                          ssd_bwd_mfma_us=round(t_mb, 1), a_shared_scan_bwd_us=round(t_sb, 1),
-                          max_abs_diff=float((a - b).abs().max()), scale=float(b.abs().max()))))
+    res = dict(d_state=N, batch=B, nseq=S, ssd_mfma_us=round(t_m, 1), a_shared_scan_us=round(t_s, 1), scan_over_mfma=round(t_s / t_m, 2),
+               mfma_GBps=round(nb / t_m / 1e3, 1), max_abs_diff=float((a - b).abs().max()), scale=float(b.abs().max()))
+    if N == 16:
+        res.update(bench_bwd())
+    print(json.dumps(res), flush=True)
