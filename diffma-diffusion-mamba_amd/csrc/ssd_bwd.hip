@@ -24,17 +24,9 @@
 // one product by 1.0 per element).  16 MFMAs and ~160 VALU per pair and orientation.  Tile epilogues turn 8 rows at a time through a 2 KB staging tile so
 // every global access is a 16-byte piece of a row.  The final d dt / dA reverse cumulative sum runs on the whole workgroup
 // (shuffle scans inside the waves, one barrier).  Measured and profiled: DESIGN.md section 3 (K6b), profiles/r02_pmc_scan_kernels.txt.
-#include "dm_mfma.h"
+#include "ssd_bwd_common.h"
 
 namespace dm {
-
-constexpr int SB_MAXL = 196;                      // longest sequence
-constexpr int SB_TILE = 32, SB_MAXT = 7;
-constexpr int SB_TAB = SB_TILE * SB_MAXT;         // 224 tile-rounded positions
-constexpr int SB_ROWS = SB_MAXL + 1;              // LDS rows of the operand arrays: row 196 is all zeros, every position past it aliases to it
-constexpr int SB_WAVES = 4;
-constexpr int SB_THREADS = 64 * SB_WAVES;
-constexpr int SB_STG = 68;                        // dwords per staging-tile row (64 + 4)
 
 // LDS map (byte offsets); rows [L, 196] of the operand arrays are zero
 constexpr int SB_XS = 0;                          // X   [197][64]  16-byte chunks XOR-swizzled by (row & 7)
@@ -42,7 +34,6 @@ constexpr int SB_GS = SB_XS + SB_ROWS * 128;      // gY  [197][64]  same layout
 constexpr int SB_BS = SB_GS + SB_ROWS * 128;      // B   [197][16]
 constexpr int SB_CS = SB_BS + SB_ROWS * 32;       // C   [197][16]
 constexpr int SB_TABS = SB_CS + SB_ROWS * 32;     // fp32 tables [T_NTAB][224]
-enum { T_DT, T_CUM, T_S2, T_ALPHA, T_GAM, T_GDT, T_SIG, T_RS, T_CS, T_NTAB };
 constexpr int SB_IDX = SB_TABS + T_NTAB * SB_TAB * 4;     // uint16 tables: z rows, dout rows
 constexpr int SB_STAGE = SB_IDX + 2 * SB_TAB * 2;         // 4 waves x [8][SB_STG] fp32
 constexpr int SB_RED = SB_STAGE + SB_WAVES * 8 * SB_STG * 4;   // block-reduction scratch
@@ -50,54 +41,10 @@ constexpr int SB_LDS_BYTES = SB_RED + 128;
 static_assert(SB_LDS_BYTES <= 80 * 1024, "two workgroups per CU");
 static_assert(SB_TABS % 16 == 0 && SB_STAGE % 16 == 0, "16-byte aligned LDS arrays");
 
-__device__ __forceinline__ void wave_lds_sync() {         // make one wave's LDS writes visible to its other lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 8 consecutive columns (chunk) of a row of the swizzled [197][64] arrays, as an MFMA operand fragment (rows >= 196: the zero row)
-__device__ __forceinline__ u32x4_t row_frag(const uint8_t* base, int row, int chunk) {
-    const int rc = row < SB_MAXL ? row : SB_MAXL;
-    return *reinterpret_cast<const u32x4_t*>(base + rc * 128 + ((chunk ^ (rc & 7)) << 4));
-}
 // 8 states of a B / C row
 __device__ __forceinline__ u32x4_t bc_frag(const uint8_t* base, int row, int kh) {
     const int rc = row < SB_MAXL ? row : SB_MAXL;
     return *reinterpret_cast<const u32x4_t*>(base + rc * 32 + kh * 16);
-}
-// One-hot selector fragment: slot e (0..7) of this lane holds 1.0, every other slot 0 (e outside 0..7: all zero)
-template <typename T>
-__device__ __forceinline__ u32x4_t one_hot(int e) {
-    constexpr uint32_t ONE = std::is_same<T, bf16_t>::value ? 0x3F80u : 0x3C00u;
-    const uint32_t v = (e & 1) ? (ONE << 16) : ONE;
-    const int d = e >> 1;
-    const bool ok = e >= 0 && e < 8;
-    return (u32x4_t){(ok && d == 0) ? v : 0u, (ok && d == 1) ? v : 0u, (ok && d == 2) ? v : 0u, (ok && d == 3) ? v : 0u};
-}
-// accumulator tile -> the two K-step fragments (8 positions each, accumulator order) of a 16-bit B-operand
-template <typename O>
-__device__ __forceinline__ void acc_to_frags(const f32x16& d, u32x4_t (&f)[2]) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-        f[ks] = (u32x4_t){O::pack(d[8 * ks], d[8 * ks + 1]), O::pack(d[8 * ks + 2], d[8 * ks + 3]), O::pack(d[8 * ks + 4], d[8 * ks + 5]),
-                            O::pack(d[8 * ks + 6], d[8 * ks + 7])};
-}
-
-// Inclusive prefix sum over the workgroup's 256 threads (one value each): six shuffle steps inside each wave, one barrier to pass
-// the wave totals on.  Every thread of the workgroup must call it.
-__device__ __forceinline__ float block_prefix_sum(float v, int lane, int w, float* wtot) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const float t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    if (lane == WAVE - 1) wtot[w] = v;
-    __syncthreads();
-    float base = 0.0f;
-#pragma unroll
-    for (int j = 0; j < SB_WAVES - 1; ++j) base += (j < w) ? wtot[j] : 0.0f;
-    return v + base;
 }
 
 template <typename T>

@@ -1179,8 +1179,8 @@ def training_loss_bwd(grad, g_eps, g_v, out_dtype):
 SSD_MFMA = os.environ.get("DIFFMA_SSD_MFMA", "1") == "1"
 # The state widths the dispatch sends to dm_ssd_fwd by default: those at which it beats the A-shared scan by 1.1 x or more at all
 # three launch sizes.  A width the C ABI serves but this tuple leaves out stays reachable through ssd_fwd() itself.  At the wide
-# states (32, 64, 128) only the forward exists: no-grad calls (sampling, EMA evaluation) take it, training takes the A-shared scan
-# pair.  Same shape as above, dm_ssd_fwd vs scan in us at nseq 24 / 192 / 768 (profiles/ssd_fwd_wide.json, one MI355X, one session):
+# states (32, 64, 128) no-grad calls (sampling, EMA evaluation) take it; training takes the A-shared scan pair unless
+# SSD_MFMA_BWD_WIDE (below) is on.  Same shape as above, dm_ssd_fwd vs scan in us at nseq 24 / 192 / 768 (profiles/ssd_fwd_wide.json, one MI355X, one session):
 #     d_state  32    32 vs 121    112 vs  281    402 vs  874      191 VGPRs,  69 KB LDS   } one 8-wave workgroup per (sequence, 4 heads),
 #     d_state  64    34 vs 122    123 vs  335    449 vs 1136      208 VGPRs,  97 KB LDS   } raw B / C rows staged in LDS: one workgroup
 #     d_state 128    38 vs 160    137 vs  872    500 vs 3264      228 VGPRs, 153 KB LDS   } per CU, 2 waves per SIMD
@@ -1239,38 +1239,66 @@ def ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_
 # Backward twin (csrc/ssd_bwd.hip): one workgroup per (sequence, head) recomputes the score tiles, nothing is saved by the
 # forward (no delta tensor, no checkpoints).  DIFFMA_SSD_MFMA_BWD=0 keeps Mamba-2 training on the A-shared scan pair.
 SSD_MFMA_BWD = os.environ.get("DIFFMA_SSD_MFMA_BWD", "1") == "1"
+# The backward at the wide states (csrc/ssd_bwd_wide.hip: one workgroup per (sequence, DM_SSD_BWD_WIDE_HEADS heads), X / gY of one
+# head in LDS, B / C fragments straight from L2).  Off by default: DIFFMA_SSD_MFMA_BWD_WIDE=1 sends Mamba-2 training at the widths
+# below to dm_ssd_fwd + dm_ssd_bwd_wide instead of the A-shared scan pair.
+SSD_MFMA_BWD_WIDE = os.environ.get("DIFFMA_SSD_MFMA_BWD_WIDE", "0") == "1"
+# The widths routed when the switch is on, by the rule above SSD_FWD_WIDTHS: a width that does not reach 1.1 x against the A-shared
+# scan backward at any of the three launch sizes leaves the tuple and stays reachable through ssd_bwd().  DiffMa-XL/2 mixer shape
+# (16 heads x 64, L 196, bf16), ssd_bwd() vs the A-shared scan backward in us at nseq 24 / 192 / 768 (profiles/ssd_bwd_wide.json, one
+# MI355X, one session):
+#     d_state  32     89 vs 187     556 vs  1162    2244 vs  4606     2.1 / 2.1 / 2.1 x     342 registers  } 67 KB LDS, one wave per
+#     d_state  64    121 vs 442     747 vs  2814    2986 vs 11137     3.7 / 3.8 / 3.7 x     382            } SIMD, no scratch; dB / dC
+#     d_state 128    176 vs 758    1105 vs  5932    4394 vs 23624     4.3 / 5.4 / 5.4 x     458            } workspace S L (H / 2) 8 N bytes
+# (d_state 16 in that session: 55 vs 104, 255 vs 337, 1014 vs 1301; its device code is the parent build's, byte for byte.)
+SSD_BWD_WIDE_WIDTHS = (32, 64, 128)
 
 
-def ssd_bwd_supported(x, L, headdim, dstate, views=()):
+def ssd_bwd_supported(x, L, headdim, dstate, views=(), gate=None):
     """The autograd node asks this before it commits the forward to the matrix pipe.  bf16 only: the kernel rounds its score and
     gradient tiles to the I/O dtype, and under fp16 autocast the GradScaler's 2^16 loss scale would push those tiles past the
-    fp16 range (the scan pair keeps every intermediate in fp32) -- the fp16 instantiation exists and is parity-tested unscaled."""
+    fp16 range (the scan pair keeps every intermediate in fp32) -- the fp16 instantiation exists and is parity-tested unscaled.
+    gate: z passed apart from `views`; at the wide states its rows need 4-byte boundaries only, as in ssd_fwd_supported."""
     if not (SSD_MFMA and SSD_MFMA_BWD and x.is_cuda and x.dtype == torch.bfloat16):
+        return False
+    wide = int(dstate) != 16
+    if wide and not (SSD_MFMA_BWD_WIDE and int(dstate) in SSD_BWD_WIDE_WIDTHS):
         return False
     for v in views:
         if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
             return False
-    return bool(_lib.load().dm_ssd_bwd_supported(int(L), int(headdim), int(dstate), dtype_code(x)))
+    if gate is not None:
+        unit, per = (4, 2) if wide else (16, 8)
+        if gate.data_ptr() % unit or gate.stride(-1) != 1 or any(st % per for st in gate.stride()[:-1]):
+            return False
+    lib = _lib.load()
+    supported = lib.dm_ssd_bwd_wide_supported if wide else lib.dm_ssd_bwd_supported
+    return bool(supported(int(L), int(headdim), int(dstate), dtype_code(x)))
 
 
 def ssd_bwd(x, Bm, Cm, dt_tok, z, dout, A_h, D_h, dt_bias_h, *, z_row_index=None, out_row_index=None, batch_per_dir=0, dx_out=None):
     """Operands as ssd_fwd; dout: [S, L, H*64] gradient of the gated output, step l read at row out_row_index[dir][l].
     Returns (dx [S, L, H*64] scan order (dx_out view if given), dz [S, L, H*64] token order per direction,
-    dBC fp32 [S, L, 32] (dB | dC, the per-head partial rows already summed), ddt fp32 [S, L, H] raw-dt gradient in token order per
-    direction, dAD fp32 [3, H]: dA | dD | d dt_bias summed over the sequences)."""
+    dBC fp32 [S, L, 2N] (dB | dC, the partial rows already summed), ddt fp32 [S, L, H] raw-dt gradient in token order per
+    direction, dAD fp32 [3, H]: dA | dD | d dt_bias summed over the sequences).  N = 16 goes to dm_ssd_bwd (partial rows per head),
+    N = 32 / 64 / 128 to dm_ssd_bwd_wide (partial rows per group of DM_SSD_BWD_WIDE_HEADS heads)."""
     _require_gpu(x, Bm, Cm, dt_tok, z, dout)
     S, L, Din = x.shape
     H = A_h.shape[0]
-    assert Din == H * 64 and Bm.shape[-1] == 16 and x.stride(2) == 1 and Bm.stride(2) == 1 and Cm.stride(2) == 1 and dt_tok.stride(2) == 1
+    N = Bm.shape[-1]
+    assert Din == H * 64 and Cm.shape[-1] == N and x.stride(2) == 1 and Bm.stride(2) == 1 and Cm.stride(2) == 1 and dt_tok.stride(2) == 1
     assert dout.shape == (S, L, Din) and dout.stride(2) == 1 and dout.dtype == x.dtype
+    entry = "dm_ssd_bwd" if N == 16 else "dm_ssd_bwd_wide"
+    HG = 1 if N == 16 else _lib.CONSTANTS["DM_SSD_BWD_WIDE_HEADS"]
+    G = (H + HG - 1) // HG                                                       # partial rows per position
     dx = dx_out if dx_out is not None else torch.empty((S, L, Din), dtype=x.dtype, device=x.device)
     dz = torch.empty((S, L, Din), dtype=x.dtype, device=x.device) if z is not None else None
-    dbc = torch.empty((H, S, L, 32), dtype=torch.float32, device=x.device)       # head-major partial rows: summed by one column sum
+    dbc = torch.empty((G, S, L, 2 * N), dtype=torch.float32, device=x.device)    # group-major partial rows: summed by one column sum
     ddt = torch.empty((S, L, H), dtype=torch.float32, device=x.device)
     dad = torch.empty((S, 3, H), dtype=torch.float32, device=x.device)
     A32, D32, b32 = _f32c(A_h), _f32c(D_h), _f32c(dt_bias_h)
     a = dm_ssd_bwd_args()
-    a.nseq, a.batch_per_dir, a.seqlen, a.nheads, a.headdim, a.dstate = S, batch_per_dir, L, H, 64, 16
+    a.nseq, a.batch_per_dir, a.seqlen, a.nheads, a.headdim, a.dstate = S, batch_per_dir, L, H, 64, N
     a.io_dtype, a.flags = dtype_code(x), 0
     a.x, a.B, a.C, a.dt, a.z, a.dout = _ptr(x), _ptr(Bm), _ptr(Cm), _ptr(dt_tok), _ptr(z), _ptr(dout)
     a.A, a.D, a.dt_bias = _ptr(A32), _ptr(D32), _ptr(b32)
@@ -1287,6 +1315,6 @@ def ssd_bwd(x, Bm, Cm, dt_tok, z, dout, A_h, D_h, dt_bias_h, *, z_row_index=None
     a.do_ss, a.do_sl = dout.stride(0), dout.stride(1)
     a.dx_ss, a.dx_sl = dx.stride(0), dx.stride(1)
     es = x.element_size()
-    _launch("dm_ssd_bwd", a, x, (6 if z is not None else 3) * S * L * Din * es + 2 * S * L * 16 * es + S * H * L * 32 * 4)
-    dbc_sum = colsum(dbc.view(H, S * L * 32)).view(S, L, 32) if H > 1 else dbc.view(S, L, 32)
+    _launch(entry, a, x, (6 if z is not None else 3) * S * L * Din * es + 2 * S * L * N * es + S * G * L * 2 * N * 4)
+    dbc_sum = colsum(dbc.view(G, S * L * 2 * N)).view(S, L, 2 * N) if G > 1 else dbc.view(S, L, 2 * N)
     return dx, dz, dbc_sum, ddt, colsum(dad.view(S, 3 * H)).view(3, H)

@@ -655,11 +655,12 @@ class _SpiralSSDFn(torch.autograd.Function):
         x, Bm, Cm = xBC[..., :Din], xBC[..., Din:Din + N], xBC[..., Din + N:]
         need_grad = grad_on and any(ctx.needs_input_grad[:7])
         ctx.ssd = False
-        if hip_ops.ssd_fwd_supported(xBC, L, P, N, views=(x, Bm, Cm), gate=z) and (not need_grad or hip_ops.ssd_bwd_supported(xBC, L, P, N)):
-            # the matrix pipe (csrc/ssd.hip, ssd_bwd.hip): single-chunk SSD as dense tile products per (sequence, head), the per-head
-            # dt read in the kernel through the gather table -- no [S, L, Din] delta tensor, no per-state recurrence, and nothing
-            # but the operands saved for the backward (which recomputes the score tiles).  The backward exists at d_state 16 only:
-            # at the wide states of hip_ops.SSD_FWD_WIDTHS a no-grad call comes here, a call that needs gradients takes the scan pair
+        if hip_ops.ssd_fwd_supported(xBC, L, P, N, views=(x, Bm, Cm), gate=z) and (not need_grad or hip_ops.ssd_bwd_supported(xBC, L, P, N, gate=z)):
+            # the matrix pipe (csrc/ssd.hip, ssd_bwd.hip, ssd_bwd_wide.hip): single-chunk SSD as dense tile products per (sequence,
+            # head), the per-head dt read in the kernel through the gather table -- no [S, L, Din] delta tensor, no per-state
+            # recurrence, and nothing but the operands saved for the backward (which recomputes the score tiles).  At d_state 16 the
+            # backward is on by default; at the wide states of hip_ops.SSD_FWD_WIDTHS a no-grad call comes here, and a call that
+            # needs gradients does only with hip_ops.SSD_MFMA_BWD_WIDE on (dm_ssd_bwd_wide) -- by default it takes the scan pair
             ydir = hip_ops.ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index=scan_index, out_row_index=scan_index,
                                    batch_per_dir=Bsz)
             out, rstd = _SpiralSSDFn._norm_merge(ydir, norm_w, eps, ndir, Bsz, L, Din)
@@ -776,8 +777,8 @@ def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias
     if zxbcdt.stride(-1) != 1:
         zxbcdt = zxbcdt.contiguous()
     # ONE autograd node, the same one the Mamba2 module runs with three directions: conv (K3), the single-chunk SSD core on the
-    # matrix pipe (dm_ssd_fwd / dm_ssd_bwd) when the shape allows it -- 16-bit I/O, headdim 64, 16-byte aligned rows, d_state 16 (or,
-    # without gradients, a wide state of hip_ops.SSD_FWD_WIDTHS) --
+    # matrix pipe (dm_ssd_fwd / dm_ssd_bwd) when the shape allows it -- 16-bit I/O, headdim 64, 16-byte aligned rows, d_state 16 (or a
+    # wide state of hip_ops.SSD_FWD_WIDTHS: without gradients, or with hip_ops.SSD_MFMA_BWD_WIDE on, dm_ssd_bwd_wide) --
     # else the A-shared selective scan, then the gated RMSNorm (dm_rmsnorm_merge_*, one slab) when rmsnorm_weight is given.
     ident = _const("ident", L, zxbcdt.device)
     y = spiral_ssd(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, rmsnorm_weight, rmsnorm_eps, ident, ident, dim, N)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 31
+#define DM_ABI_VERSION 32
 
 typedef enum {
     DM_OK = 0,
@@ -647,8 +647,7 @@ int dm_sum_partials(const dm_sum_partials_args *args, void *stream);
  * takes the A-shared scan.  d_state 16 runs one wave per (sequence, head, half) with B in registers; the wide states run
  * one 8-wave workgroup per (sequence, 4 heads) with the raw B / C rows staged in LDS (up to 153 KB of dynamic LDS).
  * At the wide states the rows of z may start on 4-byte boundaries (the gate of a two-head mixer: in_proj rows of 2 Din + 2 N + 2).
- * dm_ssd_bwd below is the backward at d_state 16 ONLY: at wide states the forward serves no-grad calls, training takes the
- * A-shared scan pair.
+ * dm_ssd_bwd below is the backward at d_state 16, dm_ssd_bwd_wide the one at the wide states.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t nseq, batch_per_dir, seqlen, nheads, headdim, dstate;
@@ -702,6 +701,18 @@ typedef struct {
 
 int dm_ssd_bwd(const dm_ssd_bwd_args *args, void *stream);
 int dm_ssd_bwd_supported(int seqlen, int headdim, int dstate, int io_dtype);
+
+/* The same backward at d_state 32, 64 and 128 (csrc/ssd_bwd_wide.hip): the same struct, the same outputs, the same roundings.
+ * One workgroup per (sequence, group of DM_SSD_BWD_WIDE_HEADS heads) walks its heads in turn and sums their dB / dC rows in fp32
+ * before they leave it (one thread per element, in head order: no atomics, two launches agree bit for bit), so
+ *   dBC_part: fp32 [ceil(nheads / DM_SSD_BWD_WIDE_HEADS)][nseq][L][2 * dstate]  per-group partial rows  dB (0 .. dstate-1) |
+ *         dC (dstate .. 2 dstate - 1) -- the caller sums over the groups (one dm_colsum_f32 over that many rows).
+ * B and C are read from global memory tile by tile, X and gY of one head live in 67 KB of LDS.  Limits: 16-bit I/O, headdim 64,
+ * 1 <= seqlen <= 196; x, B, C, dout, dx, dz rows on 16-byte boundaries, z rows on 4-byte boundaries (the gate of a two-head mixer:
+ * in_proj rows of 2 Din + 2 N + 2 elements).  dm_ssd_bwd_wide_supported() answers 0 at d_state 16, which dm_ssd_bwd serves. */
+#define DM_SSD_BWD_WIDE_HEADS 2
+int dm_ssd_bwd_wide(const dm_ssd_bwd_args *args, void *stream);
+int dm_ssd_bwd_wide_supported(int seqlen, int headdim, int dstate, int io_dtype);
 
 /* ------------------------------------------------------------------------------------------------
  * One reverse-diffusion step after the denoiser call, fused (reference diffusion/gaussian_diffusion.py:285-323

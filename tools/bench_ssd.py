@@ -1,6 +1,8 @@
 """Mamba-2 SSD forward on the matrix pipe (K6) against the A-shared scan at the DiffMa-XL/2 --use-mamba2 shape -- run on the GPU box.
-    tools/bench_ssd.py [--d-state N] [batch ...]      N in 16 (default) / 32 / 64 / 128; at the wide states only the forward pair
-is timed (the matrix-pipe backward is d_state 16 only)."""
+    tools/bench_ssd.py [--d-state N] [batch ...]      N in 16 (default) / 32 / 64 / 128
+Both pairs are timed at every width: dm_ssd_fwd against the A-shared scan forward, and the matrix-pipe backward (dm_ssd_bwd at 16,
+dm_ssd_bwd_wide at 32 / 64 / 128, called through hip_ops.ssd_bwd whatever the routing switches say) against the A-shared scan
+backward.  The backward pair alternates three windows of at least 0.1 s each and reports the medians and the spread."""
 import argparse, os, sys, json
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -67,8 +69,21 @@ for B in args.batches:
             return hip_ops.scan_bwd(x, dtg, A, Bm, Cm, Dp, z, bp, dout, ckpt, True, z_row_index=idx, out_row_index=idx, batch_per_dir=B, dout_per_seq=True,
                                     du_out=dxBC[..., :Din], a_shared=True, dbc_out=dxBC[..., Din:])
 
-        t_mb, t_sb = timeit(mfma_bwd), timeit(scan_bwd)
-        return dict(ssd_bwd_mfma_us=round(t_mb, 1), a_shared_scan_bwd_us=round(t_sb, 1))
+        mfma_bwd()
+        scan_bwd()
+        iters = lambda fn: max(10, int(1e5 / timeit(fn, 5)))                   # a window of 0.1 s or more
+        n_m, n_s = iters(mfma_bwd), iters(scan_bwd)
+        t_mb, t_sb = [], []
+        for _ in range(3):                                                     # alternate the two: other work shares the host
+            t_mb.append(timeit(mfma_bwd, n_m))
+            t_sb.append(timeit(scan_bwd, n_s))
+        med = lambda v: sorted(v)[1]
+        spread = lambda v: round((max(v) - min(v)) / med(v), 3)
+        HG = 1 if N == 16 else hip_ops._lib.CONSTANTS["DM_SSD_BWD_WIDE_HEADS"]
+        GC = 256 if N == 16 else 4096 // N                                     # channels per scan-backward launch group (README "Shapes")
+        return dict(ssd_bwd_mfma_us=round(med(t_mb), 1), a_shared_scan_bwd_us=round(med(t_sb), 1), scan_bwd_over_mfma_bwd=round(med(t_sb) / med(t_mb), 2),
+                    spread_mfma=spread(t_mb), spread_scan=spread(t_sb), mfma_dbc_workspace_bytes=-(-H // HG) * S * L * 8 * N,
+                    scan_dbc_workspace_bytes=-(-Din // GC) * S * L * 8 * N)
 
     a = mfma().float().clone()
     b = scan().float()
@@ -76,6 +91,5 @@ for B in args.batches:
     t_m, t_s = timeit(mfma), timeit(scan)
     res = dict(d_state=N, batch=B, nseq=S, ssd_mfma_us=round(t_m, 1), a_shared_scan_us=round(t_s, 1), scan_over_mfma=round(t_s / t_m, 2),
                mfma_GBps=round(nb / t_m / 1e3, 1), max_abs_diff=float((a - b).abs().max()), scale=float(b.abs().max()))
-    if N == 16:
-        res.update(bench_bwd())
+    res.update(bench_bwd())
     print(json.dumps(res), flush=True)
