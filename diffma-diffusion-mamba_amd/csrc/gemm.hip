@@ -204,6 +204,7 @@ static void gemm_launch_t(const dm_gemm_args& a, const dm_gemm_args* second, hip
 
 static int check_gemm(const dm_gemm_args& a) {
     if (!a.a || !a.b || !a.c) { set_error("dm_gemm: null tensor pointer"); return DM_ERR_ARG; }
+    if (a.gate_z) { set_error("dm_gemm: the gated epilogue (gate_z) belongs to dm_gemm_large"); return DM_ERR_ARG; }
     if (!dm_gemm_supported(a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype)) {
         set_error("dm_gemm: unsupported shape / dtype (P %d Q %d Kc %d, a_kmajor %d b_kmajor %d, dtypes %d -> %d): 16-bit operands, "
                   "Q %% 8 == 0, and the contiguous index of every operand a multiple of 8", a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype);

@@ -41,6 +41,23 @@ struct gl_args {
     int MB, NT, T, TX;           // row blocks, column tiles, tiles, tiles per XCD
 };
 
+// The gated epilogue (dm_gemm_large with gate_z set): the C tile is the out_proj input gradient dy and never leaves the CU -- what is stored is
+// the hoisted gate's backward of it, g = dy silu(z) and dz = dy pre silu'(z) (merge.hip, dm_gate_bwd), from z and pre rows fetched
+// under the next tile's products.  A second kernel argument: the plain kernel's kernarg layout stays what it was.
+// Wait states behind the epilogue's two 16-byte stores (gate_piece).  The ISA's table of manually inserted wait states lists ONE
+// between a vector-memory store of more than 64 bits and a vector instruction that overwrites its data registers; the compiler's
+// hazard recogniser leaves stores whose scalar offset is a register out of that rule, and the epilogue's stores are such stores.
+// Measured on the MI355X: with the next piece's arithmetic directly behind the store, 3.4 % of g and 0.2 % of dz arrived overwritten
+// (later lane quads, first or second word); with 1, 8, 16, 32 or 64 wait states, none of 50 M elements.  Two: twice the table's figure.
+#ifndef GL_GATE_IDLE_ASM
+#define GL_GATE_IDLE_ASM "s_nop 1"
+#endif
+struct gl_gate_args {
+    const void *z, *pre;
+    void *g, *dz;
+    int ldz, ldp;                // elements: row strides of z and dz, of pre and g
+};
+
 typedef __attribute__((address_space(3))) void* gl_lds_ptr;
 
 __device__ __forceinline__ void gl_swap32(uint32_t& a, uint32_t& b) {        // a[lanes 32..63] <-> b[lanes 0..31]
@@ -49,14 +66,32 @@ __device__ __forceinline__ void gl_swap32(uint32_t& a, uint32_t& b) {        // 
     b = r[1];
 }
 
+// One element of dm_gate_bwd (merge.hip, gate_bwd_kernel): the same expressions in the same order on the same sigmoid_f.
+__device__ __forceinline__ void gl_gate_elem(float dy, float z, float pre, float& g, float& dz) {
+    const float sg = sigmoid_f(z);
+    g = dy * z * sg;
+    dz = dy * pre * sg * (1.0f + z * (1.0f - sg));
+}
+template <typename T>
+__device__ __forceinline__ void gl_gate_word(uint32_t dyw, uint32_t zw, uint32_t pw, uint32_t& gw, uint32_t& dzw) {
+    float d0, d1, z0, z1, p0, p1, g0, g1, q0, q1;
+    mfma<T>::unpack(dyw, d0, d1);
+    mfma<T>::unpack(zw, z0, z1);
+    mfma<T>::unpack(pw, p0, p1);
+    gl_gate_elem(d0, z0, p0, g0, q0);
+    gl_gate_elem(d1, z1, p1, g1, q1);
+    gw = mfma<T>::pack(g0, g1);
+    dzw = mfma<T>::pack(q0, q1);
+}
+
 // The running position of the operand stream: which of this workgroup's tiles, which K-step.
 struct gl_cursor {
     int tile, kt;                // index into the workgroup's own tile list, K-step inside the tile
     int soff_a, soff_b;          // byte offsets of the tile's first slice (rows m0 / n0, k = 0)
 };
 
-template <typename T, bool NT_STORE = true>
-__global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args p) {
+template <typename T, bool NT_STORE, bool GATED>
+__device__ __forceinline__ void gl_body(const gl_args& p, const gl_gate_args& e) {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[GL_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;                       // wave tile: rows 64 wm .. + 64, columns 128 wn .. + 128
@@ -108,10 +143,18 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
         const int sb = live ? ld.soff_b + ld.kt * (GL_BK * 2) : 0x7ffffff0;
         uint8_t* la = lds + stage * GL_SLICE + lds_w;
         uint8_t* lb = lds + GL_B0 + stage * GL_SLICE + lds_w;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la), 16, voa[0], sa, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la + 1024), 16, voa[1], sa, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb), 16, vob[0], sb, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb + 1024), 16, vob[1], sb, 0, 0);
+        if constexpr (GATED) {
+            // (the second row group is 16 rows on: a wave-uniform distance, carried by the scalar offset -- two registers less)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la), 16, voa[0], sa, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la + 1024), 16, voa[0], live ? sa + 32 * p.lda : sa, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb), 16, vob[0], sb, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb + 1024), 16, vob[0], live ? sb + 32 * p.ldb : sb, 0, 0);
+        } else {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la), 16, voa[0], sa, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (gl_lds_ptr)(la + 1024), 16, voa[1], sa, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb), 16, vob[0], sb, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (gl_lds_ptr)(lb + 1024), 16, vob[1], sb, 0, 0);
+        }
         ++lg;
         if (++ld.kt == KT) {
             ld.kt = 0;
@@ -145,9 +188,13 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
     // ---- the finished C tile waits in 16 x 16-byte pieces per lane (the "stash") and leaves ONE piece per K-step of the next tile:
     // the write stream is even in time (a burst of 128 KB per CU at every tile end would queue in front of the operand loads, which
     // share the in-order vmcnt counter with it) ----
-    u32x4_t stash[16];
+    // GATED: pieces 12..15 (the last 32 x 128-byte round) stay in the wave's staging rows until their K-step and the 16 registers
+    // hold the (z, pre) piece of the next K-step (eight) and the epilogue's temporaries instead: the register count of the plain
+    // kernel leaves no room for both.
+    constexpr int NSTASH = GATED ? 12 : 16;
+    u32x4_t stash[NSTASH];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) stash[i] = (u32x4_t){0u, 0u, 0u, 0u};
+    for (int i = 0; i < NSTASH; ++i) stash[i] = (u32x4_t){0u, 0u, 0u, 0u};
     int soc_st = 0, c_live = 0;                                    // C origin of the stashed tile; its descriptor size (0: nothing to store)
     // A lane holds, of the 32 x 32 block (i, j) of the wave's 64 x 128 tile, row 32 j + (l & 31), columns 32 i + 8 q + 4 (l >> 5) + 0..3:
     // stored like that, every store instruction would write 32-byte pieces of 32 different rows, and with the pieces of a row
@@ -186,7 +233,10 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) stash[j * 8 + h * 4 + k] = *reinterpret_cast<const u32x4_t*>(tw + tw_r + k * 1024);
+                for (int k = 0; k < 4; ++k) {
+                    const int pc = j * 8 + h * 4 + k;                      // GATED: the last round is read piece by piece (gate_piece)
+                    if (pc < NSTASH) stash[pc < NSTASH ? pc : 0] = *reinterpret_cast<const u32x4_t*>(tw + tw_r + k * 1024);
+                }
             }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -203,11 +253,80 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
         __builtin_amdgcn_raw_buffer_store_b128(stash[pc], rc, voc + h * 128, soc_st + (32 * j + 8 * k) * p.ldc * 2, NT_STORE ? 2 : 0);
     };
 
+    // ---- GATED: piece pc of the stashed tile is dy; with the matching 16 bytes of z and pre it leaves as g and dz (two stores), dy
+    // itself is not written.  z, pre, g and dz are row-major and share the tile's (row, column) origin; dz has the row stride of z
+    // (the z halves of xz and d(xz)) and g that of pre, so two lane offsets serve the four tensors: the wave-uniform part of an
+    // address rides in the scalar offset, the lane's part is (l >> 3) rows + 16 (l & 7) bytes.
+    // (z, pre) of piece pc are requested ONE K-step ahead, right behind piece pc - 1's turn, into eight registers (with the four
+    // pieces that stay in LDS the kernel holds what the plain one holds); in vmcnt order they sit behind the operand loads of
+    // K-step g + 2, which are thereby waited for half a step earlier than in the plain kernel.
+    u32x4_t zq[2];                                                 // z, pre
+    zq[0] = zq[1] = (u32x4_t){0u, 0u, 0u, 0u};
+    int st_row = 0, st_col = 0, cur_tile = 0;                      // origin of the stashed tile; list index of the tile in the accumulators
+    const int vo_z = ((lane >> 3) * e.ldz + 8 * (lane & 7)) * 2, vo_p = ((lane >> 3) * e.ldp + 8 * (lane & 7)) * 2;
+    const int zb = (int)(((int64_t)(p.M - 1) * e.ldz + p.N) * 2), pb = (int)(((int64_t)(p.M - 1) * e.ldp + p.N) * 2);
+    auto e_soff = [&](int pc, int row0, int col0, int ldx) {
+        const int j = pc >> 3, h = (pc >> 2) & 1, k = pc & 3;
+        return ((row0 + 64 * wm + 32 * j + 8 * k) * ldx + col0 + 128 * wn + 64 * h) * 2;
+    };
+    auto e_rsrc = [&](const void* base, int bytes) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000); };
+    auto zp_load = [&](int pc, int row0, int col0, bool live) {    // size 0: the loads return zeros (but are counted)
+        zq[0] = __builtin_amdgcn_raw_buffer_load_b128(e_rsrc(e.z, live ? zb : 0), vo_z, e_soff(pc, row0, col0, e.ldz), 2);
+        zq[1] = __builtin_amdgcn_raw_buffer_load_b128(e_rsrc(e.pre, live ? pb : 0), vo_p, e_soff(pc, row0, col0, e.ldp), 2);
+    };
+    auto gate_piece = [&](int pc, bool live, auto&& next_loads) {
+        const u32x4_t dyv = stash[pc < NSTASH ? pc : pc - NSTASH];
+        u32x4_t gv, dzv;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {                              // one word (two elements) at a time: few temporaries
+            uint32_t gw, dzw;
+            gl_gate_word<T>(dyv[w], zq[0][w], zq[1][w], gw, dzw);
+            gv[w] = gw;
+            dzv[w] = dzw;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        next_loads();                                              // ahead of the stores: their wait then leaves the stores in flight
+        const int so_g = e_soff(pc, st_row, st_col, e.ldp), so_dz = e_soff(pc, st_row, st_col, e.ldz);
+        const rsrc_t rg = e_rsrc(e.g, live ? pb : 0), rdz = e_rsrc(e.dz, live ? zb : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_raw_buffer_store_b128(gv, rg, vo_p, so_g, 2);
+        __builtin_amdgcn_raw_buffer_store_b128(dzv, rdz, vo_z, so_dz, 2);
+        // gv and dzv are rewritten by the next piece at once -- unlike the plain kernel's stash pieces -- and nothing in the hardware
+        // or the compiler holds a vector instruction back from the data registers of the store in front of it (GL_GATE_IDLE_ASM above)
+        asm volatile(GL_GATE_IDLE_ASM ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // K-step J of a group: pieces 12 .. 15 come out of the staging rows one step before their turn, into the registers of pieces
+    // 0 .. 3 (gone by then); (z, pre) of piece J + 1 are requested -- at step 15 that is piece 0 of the tile in the accumulators,
+    // whose stash begins behind this group when it is the tile's last (next_live); piece J leaves.
+    auto gate_step = [&](int J, bool live, bool next_live, bool drain) {
+        if (J + 1 >= NSTASH && J + 1 < 16) stash[J + 1 - NSTASH] = *reinterpret_cast<const u32x4_t*>(tw + tw_r + (J + 1 - NSTASH) * 1024);
+        gate_piece(J, live, [&]() {
+            if (J + 1 < 16) zp_load(J + 1, st_row, st_col, live);
+        });
+        if (J + 1 == 16 && !drain) {                               // (behind piece 15: st_row / st_col are free to move on)
+            const int t = t0 + 32 * cur_tile, mb = t / p.NT;
+            if (next_live) {
+                st_row = mb * GL_BM;
+                st_col = (t - mb * p.NT) * GL_BN;
+            }
+            zp_load(0, st_row, st_col, next_live);
+        }
+    };
+
     // ---- prologue: three K-steps in flight, the first two landed ----
     issue_loads(0);
     issue_loads(1);
     issue_loads(2);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    if constexpr (GATED) {
+        // as many operations as step -1 would have queued behind them (four, here stores of size 0: dropped, but counted): the
+        // counted wait of EVERY step then sees the same queue
+#pragma unroll
+        for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(zq[0], e_rsrc(e.g, 0), 0, 0, 2);
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    }
     __builtin_amdgcn_s_barrier();
     u32x4_t fx0[2], fx1[2], fw[4];
 #pragma unroll
@@ -236,12 +355,15 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
     }
     // One K-step at position J of a 16-step group (ring stage J & 3, stash piece J).  Queue behind the loads of K-step g + 2 when the
     // wait is reached: store (g - 1), 4 loads (g + 3), store (g) -> vmcnt(6), always (stores of an empty stash are issued and dropped).
+    // GATED: 2 loads of (z, pre) (g), 2 stores (g - 1), 4 loads (g + 3), 2 loads (g + 1), 2 stores (g) -> vmcnt(12); the wait for
+    // (z, pre) (g) in the middle of step g has emptied the queue down to the stores of step g - 1 already.
 #define GL_STEP(J)                                                                                                           \
     {                                                                                                                        \
         GL_HALF(fx0, fx1, (J) & 3, 1)                                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
         issue_loads(((J) + 3) & 3);                                                                                          \
-        store_piece(J, st_bytes);                                                                                            \
+        if constexpr (GATED) gate_step(J, st_bytes != 0, last_group, false);                                                 \
+        else store_piece(J, st_bytes);                                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
         GL_HALF(fx1, fx0, ((J) + 1) & 3, 0)                                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
@@ -250,12 +372,14 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
             soc_st = soc_c;                                                                                                  \
             c_live = c_bytes;                                                                                                \
         }                                                                                                                    \
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                                                     \
+        if constexpr (GATED) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");                                               \
+        else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                                                \
         __builtin_amdgcn_s_barrier();                                                              \
     }
 
     for (int ct = 0; ct < ntile; ++ct) {
         tile_origin(ct, soa_c, sob_c, soc_c);
+        cur_tile = ct;
         for (int kg = 0; kg < KG; ++kg) {
             const int st_bytes = kg == 0 ? c_live : 0;            // the stash leaves during the first 16 steps of the next tile
             const bool last_group = kg == KG - 1;
@@ -267,7 +391,20 @@ __global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args
 #undef GL_HALF
     // the last tile
 #pragma unroll
-    for (int pc = 0; pc < 16; ++pc) store_piece(pc, c_live);
+    for (int pc = 0; pc < 16; ++pc) {
+        if constexpr (GATED) gate_step(pc, c_live != 0, false, true);
+        else store_piece(pc, c_live);
+    }
+}
+
+template <typename T, bool NT_STORE = true>
+__global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_kernel(const gl_args p) {
+    gl_body<T, NT_STORE, false>(p, gl_gate_args{});
+}
+
+template <typename T>
+__global__ __launch_bounds__(GL_THREADS, 2) void gemm_large_gated_kernel(const gl_args p, const gl_gate_args e) {
+    gl_body<T, true, true>(p, e);
 }
 
 static bool gl_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, int ab_dtype, int c_dtype) {
@@ -277,16 +414,116 @@ static bool gl_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, int a
     return true;
 }
 
+// Row blocks that the persistent kernel takes (see dm_gemm_large below): whole rounds of 256 tiles, unless what is left is half a round or more.
+static int gl_main_blocks(int P, int Q) {
+    const int NT = Q / GL_BN, MB = (P + GL_BM - 1) / GL_BM;
+    int q = 256, y = NT;
+    while (y) { const int r = q % y; q = y; y = r; }     // gcd(256, NT)
+    q = 256 / q;                                           // row blocks in a whole number of rounds
+    int MB_main = MB / q * q;
+    if (MB_main == 0 || (MB - MB_main) * NT >= 128) MB_main = MB;
+    return MB_main;
+}
+
+static gl_args gl_plan(const void* pa, const void* pb, void* pc, int P, int Q, int Kc, int64_t lda, int64_t ldb, int64_t ldc, int MB_main) {
+    const int MB = (P + GL_BM - 1) / GL_BM;
+    gl_args g;
+    g.a = pa; g.b = pb; g.c = pc;
+    g.M = MB_main == MB ? P : MB_main * GL_BM;
+    g.N = Q; g.K = Kc;
+    g.lda = (int)lda; g.ldb = (int)ldb; g.ldc = (int)ldc;
+    g.MB = MB_main;
+    g.NT = Q / GL_BN;
+    g.T = g.MB * g.NT;
+    const int mb_x = (g.MB + 7) / 8;                       // whole row blocks per XCD: a row block's column tiles share one L2
+    g.TX = mb_x * g.NT;
+    return g;
+}
+
 }  // namespace dm
 
 extern "C" int dm_gemm_large_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, int ab_dtype, int c_dtype) {
     return dm::gl_supported(P, Q, Kc, a_kmajor, b_kmajor, ab_dtype, c_dtype) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// dm_gemm_large with gate_z set -- the out_proj input gradient with the hoisted gate's backward in its epilogue (include/diffma_hip.h).
+// ------------------------------------------------------------------------------------------------------------
+extern "C" int dm_gemm_large_gated_supported(int P, int Q, int Kc, int ab_dtype) {
+    return dm::gl_supported(P, Q, Kc, 1, 1, ab_dtype, ab_dtype) ? 1 : 0;
+}
+
+extern "C" int dm_gemm_large_tail_rows(int P, int Q) {
+    if (P <= 0 || Q < dm::GL_BN || Q % dm::GL_BN) return 0;
+    const int MB = (P + dm::GL_BM - 1) / dm::GL_BM, MB_main = dm::gl_main_blocks(P, Q);
+    return MB_main == MB ? 0 : P - MB_main * dm::GL_BM;
+}
+
+static int gl_run_gated(const dm_gemm_args& a, void* stream) {
+    using namespace dm;
+    if (a.c_dtype != a.ab_dtype && (a.ab_dtype == DM_BF16 || a.ab_dtype == DM_F16)) {
+        set_error("dm_gemm_large (gated): g and dz take the operand dtype (c_dtype %d, ab_dtype %d)", a.c_dtype, a.ab_dtype);
+        return DM_ERR_ARG;
+    }
+    if (a.accumulate || !a.a_kmajor || !a.b_kmajor) { set_error("dm_gemm_large (gated): k-major operands, no accumulation"); return DM_ERR_ARG; }
+    if (!a.a || !a.b || !a.gate_z || !a.gate_pre || !a.gate_g || !a.gate_dz) { set_error("dm_gemm_large (gated): null tensor pointer"); return DM_ERR_ARG; }
+    if (!(a.ab_dtype == DM_BF16 || a.ab_dtype == DM_F16)) {
+        set_error("dm_gemm_large (gated): dtype %d: 16-bit tensors only (bf16 / fp16)", a.ab_dtype);
+        return DM_ERR_DTYPE;
+    }
+    if (!gl_supported(a.P, a.Q, a.Kc, 1, 1, a.ab_dtype, a.ab_dtype)) {
+        set_error("dm_gemm_large (gated): unsupported shape (P %d Q %d Kc %d): P >= 2048, Q %% 256 == 0, Kc %% 512 == 0", a.P, a.Q, a.Kc);
+        return DM_ERR_ARG;
+    }
+    const int tail = dm_gemm_large_tail_rows(a.P, a.Q);
+    if (tail && !a.c) { set_error("dm_gemm_large (gated): %d rows go to the small-launch kernel and need c as their dy slice", tail); return DM_ERR_ARG; }
+    auto big = [&](int64_t ld, int cols) { return ((int64_t)(a.P - 1) * ld + cols) * 2 + (int64_t)GL_BM * ld * 2 >= (int64_t)0x7ffffff0; };
+    auto bad = [&](const void* ptr, int64_t ld, int cols) { return ld < cols || ld % 8 || ((uintptr_t)ptr % 16) || big(ld, cols); };
+    if (bad(a.a, a.lda, a.Kc) || bad(a.b, a.ldb, a.Kc) || (int64_t)a.Q * a.ldb * 2 >= (int64_t)0x7ffffff0 || bad(a.gate_z, a.gate_ldz, a.Q) ||
+        bad(a.gate_pre, a.gate_ldp, a.Q) || bad(a.gate_g, a.gate_ldg, a.Q) || bad(a.gate_dz, a.gate_lddz, a.Q) || (tail && bad(a.c, a.ldc, a.Q))) {
+        set_error("dm_gemm_large (gated): row strides must cover a row and be multiples of 8 elements, tensors 16-byte aligned and below 2 GB");
+        return DM_ERR_LAYOUT;
+    }
+    if (a.gate_lddz != a.gate_ldz || a.gate_ldg != a.gate_ldp) {
+        set_error("dm_gemm_large (gated): dz takes the row stride of z and g that of pre (lddz %lld ldz %lld, ldg %lld ldp %lld)",
+                  (long long)a.gate_lddz, (long long)a.gate_ldz, (long long)a.gate_ldg, (long long)a.gate_ldp);
+        return DM_ERR_LAYOUT;
+    }
+    const int MB_main = gl_main_blocks(a.P, a.Q);
+    const gl_args g = gl_plan(a.a, a.b, nullptr, a.P, a.Q, a.Kc, a.lda, a.ldb, a.Q, MB_main);
+    gl_gate_args e;
+    e.z = a.gate_z; e.pre = a.gate_pre; e.g = a.gate_g; e.dz = a.gate_dz;
+    e.ldz = (int)a.gate_ldz; e.ldp = (int)a.gate_ldp;
+    hipStream_t st = (hipStream_t)stream;
+    if (a.ab_dtype == DM_BF16) hipLaunchKernelGGL((gemm_large_gated_kernel<bf16_t>), dim3(256), dim3(GL_THREADS), 0, st, g, e);
+    else hipLaunchKernelGGL((gemm_large_gated_kernel<f16_t>), dim3(256), dim3(GL_THREADS), 0, st, g, e);
+    if (tail) {
+        // the rows beyond the whole rounds keep the two launches: K11 into the caller's dy slice, then dm_gate_bwd on that slice
+        const int64_t r0 = (int64_t)MB_main * GL_BM;
+        dm_gemm_args t = {};
+        t.P = tail; t.Q = a.Q; t.Kc = a.Kc;
+        t.ab_dtype = t.c_dtype = a.ab_dtype;
+        t.a_kmajor = t.b_kmajor = 1;
+        t.a = (const char*)a.a + r0 * a.lda * 2; t.b = a.b; t.c = a.c;
+        t.lda = a.lda; t.ldb = a.ldb; t.ldc = a.ldc;
+        int rc = dm_gemm(&t, stream);
+        if (rc != DM_OK) return rc;
+        dm_gate_bwd_args gb = {};
+        gb.batch = 1; gb.seqlen = tail; gb.dim = a.Q; gb.io_dtype = a.ab_dtype;
+        gb.dy = a.c; gb.z = (const char*)a.gate_z + r0 * a.gate_ldz * 2; gb.pre = (const char*)a.gate_pre + r0 * a.gate_ldp * 2;
+        gb.g = (char*)a.gate_g + r0 * a.gate_ldg * 2; gb.dz = (char*)a.gate_dz + r0 * a.gate_lddz * 2;
+        gb.dy_sl = a.ldc; gb.z_sl = a.gate_ldz; gb.p_sl = a.gate_ldp; gb.g_sl = a.gate_ldg; gb.dz_sl = a.gate_lddz;
+        rc = dm_gate_bwd(&gb, stream);
+        if (rc != DM_OK) return rc;
+    }
+    return launch_status("dm_gemm_large (gated)");
+}
+
 extern "C" int dm_gemm_large(const dm_gemm_args* args, void* stream) {
     using namespace dm;
     if (!args) { set_error("dm_gemm_large: null args"); return DM_ERR_ARG; }
     const dm_gemm_args& a = *args;
+    if (a.gate_z) return gl_run_gated(a, stream);          // the gated epilogue (below)
     if (!a.a || !a.b || !a.c) { set_error("dm_gemm_large: null tensor pointer"); return DM_ERR_ARG; }
     if (!gl_supported(a.P, a.Q, a.Kc, a.a_kmajor, a.b_kmajor, a.ab_dtype, a.c_dtype) || a.accumulate) {
         set_error("dm_gemm_large: unsupported (P %d Q %d Kc %d, kmajor %d %d, dtypes %d -> %d, accumulate %d): both operands k-major, "
@@ -303,23 +540,10 @@ extern "C" int dm_gemm_large(const dm_gemm_args* args, void* stream) {
     }
     // Whole rounds only: 256 persistent workgroups take 256 tiles at a time, so a tile count just above a multiple of 256 would cost a
     // whole extra round (out_proj forward: 392 row blocks x 2 column tiles = 3.06 rounds).  The row blocks beyond the last whole round
-    // -- when they are less than half a round -- go to the small-launch kernel K11 (dm_gemm) behind this one, on the same stream.
-    const int NT = a.Q / GL_BN, MB = (a.P + GL_BM - 1) / GL_BM;
-    int q = 256, y = NT;
-    while (y) { const int r = q % y; q = y; y = r; }     // gcd(256, NT)
-    q = 256 / q;                                           // row blocks in a whole number of rounds
-    int MB_main = MB / q * q;
-    if (MB_main == 0 || (MB - MB_main) * NT >= 128) MB_main = MB;
-    gl_args g;
-    g.a = a.a; g.b = a.b; g.c = a.c;
-    g.M = MB_main == MB ? a.P : MB_main * GL_BM;
-    g.N = a.Q; g.K = a.Kc;
-    g.lda = (int)a.lda; g.ldb = (int)a.ldb; g.ldc = (int)a.ldc;
-    g.MB = MB_main;
-    g.NT = NT;
-    g.T = g.MB * g.NT;
-    const int mb_x = (g.MB + 7) / 8;                       // whole row blocks per XCD: a row block's column tiles share one L2
-    g.TX = mb_x * g.NT;
+    // -- when they are less than half a round -- go to the small-launch kernel K11 (dm_gemm) behind this one, on the same stream
+    // (gl_main_blocks).
+    const int MB = (a.P + GL_BM - 1) / GL_BM, MB_main = gl_main_blocks(a.P, a.Q);
+    const gl_args g = gl_plan(a.a, a.b, a.c, a.P, a.Q, a.Kc, a.lda, a.ldb, a.ldc, MB_main);
     hipStream_t st = (hipStream_t)stream;
     if (a.ab_dtype == DM_BF16) hipLaunchKernelGGL((gemm_large_kernel<bf16_t>), dim3(256), dim3(GL_THREADS), 0, st, g);
     else hipLaunchKernelGGL((gemm_large_kernel<f16_t>), dim3(256), dim3(GL_THREADS), 0, st, g);
@@ -333,3 +557,4 @@ extern "C" int dm_gemm_large(const dm_gemm_args* args, void* stream) {
     }
     return launch_status("dm_gemm_large");
 }
+

@@ -858,6 +858,52 @@ def gemm_large(a, b, out=None):
     return out
 
 
+# The out_proj input gradient with the hoisted gate's backward in K12's epilogue (dm_gemm_large with gate_z set): dy never reaches memory.
+# DIFFMA_GATE_IN_DGRAD=0 returns the mixer backward to its two launches (dm_gemm_large, then dm_gate_bwd).
+GATE_IN_DGRAD = os.environ.get("DIFFMA_GATE_IN_DGRAD", "1") == "1"
+
+
+def _rows16(t):
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
+
+
+def gemm_large_gated_supported(a, b, z, pre, dz_out):
+    """a [P, Kc], b [Q, Kc] as gemm_large_supported; z, pre, dz_out: [P, Q] row-major views of a's dtype, dz_out with z's row stride,
+    pre contiguous (g is allocated like it)."""
+    if not (GATE_IN_DGRAD and gemm_large_supported(a, b)):
+        return False
+    P, Q = a.shape[0], b.shape[0]
+    for t in (z, pre, dz_out):
+        if not (t.is_cuda and t.dtype == a.dtype and tuple(t.shape) == (P, Q) and _rows16(t)) or (P + 256) * t.stride(0) * 2 >= 0x7ffffff0:
+            return False
+    if dz_out.stride(0) != z.stride(0) or pre.stride(0) != Q:
+        return False
+    return bool(_lib.load().dm_gemm_large_gated_supported(P, Q, a.shape[1], dtype_code(a)))
+
+
+def gemm_large_gated(a, b, z, pre, dz_out):
+    """With dy = a @ b^T (never stored): returns g = dy * silu(z) [P, Q] and writes dz_out = dy * pre * silu'(z); bit for bit
+    gemm_large followed by gate_bwd.  The caller checked gemm_large_gated_supported."""
+    _require_gpu(a, b, z, pre, dz_out)
+    P, Kc = a.shape
+    Q = b.shape[0]
+    g = torch.empty((P, Q), dtype=a.dtype, device=a.device)
+    tail = int(_lib.load().dm_gemm_large_tail_rows(P, Q))
+    dy_tail = torch.empty((tail, Q), dtype=a.dtype, device=a.device) if tail else None
+    s = dm_gemm_args()                   # gate_z set: the gated epilogue (c / ldc: the remainder's dy slice)
+    s.P, s.Q, s.Kc = P, Q, Kc
+    s.ab_dtype = s.c_dtype = dtype_code(a)
+    s.a_kmajor, s.b_kmajor, s.accumulate = 1, 1, 0
+    s.a, s.b, s.gate_z, s.gate_pre, s.gate_g, s.gate_dz = _ptr(a), _ptr(b), _ptr(z), _ptr(pre), _ptr(g), _ptr(dz_out)
+    s.lda, s.ldb = a.stride(0), b.stride(0)
+    s.gate_ldz, s.gate_ldp, s.gate_ldg, s.gate_lddz = z.stride(0), pre.stride(0), g.stride(0), dz_out.stride(0)
+    if tail:
+        s.c, s.ldc = _ptr(dy_tail), Q
+    es = a.element_size()
+    _launch("dm_gemm_large", s, a, (P * Kc + Q * Kc + 4 * P * Q) * es, flops=2 * P * Q * Kc)
+    return g
+
+
 LN_ROWS_PER_BLOCK = _lib.DM_LN_ROWS_PER_BLOCK
 LN_SMALL_ROWS = int(os.environ.get("DIFFMA_LN_SMALL_ROWS", "4"))     # rows per partial-sum group of the backward when a launch has few rows; 0: always 28
 

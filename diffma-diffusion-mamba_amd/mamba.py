@@ -18,7 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .selective_scan_interface import linear_pair, linear_splitk, spiral_ssm, spiral_ssm_pair, spiral_ssm_pair_supported
+from .selective_scan_interface import (gate_in_dgrad_wanted, linear_pair, linear_splitk, spiral_ssm, spiral_ssm_out_proj, spiral_ssm_pair,
+                                       spiral_ssm_pair_supported)
 from .tools import efficient_scan_tokens
 
 
@@ -112,6 +113,10 @@ class Mamba(nn.Module):
             raise ValueError(f"sequence length {hidden_states.shape[1]} != spiral table length {self.scan_index.shape[1]}")
         xz = linear_splitk(hidden_states, self.in_proj.weight, self.in_proj.bias)      # [B, L, 2*Din] token-major
         A = self._A_now(xz)
+        if self.out_proj.bias is None and gate_in_dgrad_wanted(xz, self.out_proj.weight):
+            # large batch: the gate's backward inside out_proj's input gradient (dm_gemm_large, gated)
+            return spiral_ssm_out_proj(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
+                                       self.dt_proj.bias, A, self.D, self.scan_index, self.out_proj.weight)
         y = spiral_ssm(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
                        self.dt_proj.bias, A, self.D, self.scan_index)
         return linear_splitk(y.to(xz.dtype), self.out_proj.weight, self.out_proj.bias)

@@ -307,29 +307,37 @@ class _LinearSplitKFn(torch.autograd.Function):
                 dy2 = dy2.to(xc.dtype)
             x2 = xc.reshape(-1, xc.shape[-1])
             dy2c, x2c = dy2.contiguous(), x2.contiguous()
-            if not ctx.needs_input_grad[0]:
-                dx = None
-            elif b_dt is None and _own_single(dy2c, wc, True, False):
-                dx = hip_ops.gemm(dy2c, wc, True, False).view(xc.shape).to(x_dt)
-            elif LARGE_DGRAD_NT and dy2c.is_cuda and dy2c.shape[0] >= LARGE_MIN_ROWS and dy2c.dtype in (torch.bfloat16, torch.float16):
-                # dx = dy W as an "NT" product with a transposed 16-bit copy of the weight (a few MB, one small launch): both
-                # operands then have the contraction index contiguous.  Measured at M = 100 352 (tools/bench_gemm_large.py): the
-                # library's NN form 217 / 148 us (in_proj / out_proj) against 198 / 125 us for its NT form and 223 / 108 us for K12.
-                wt = wc.t().contiguous()
-                if _own_large(dy2c, wt):
-                    dx = hip_ops.gemm_large(dy2c, wt).view(xc.shape).to(x_dt)
-                else:
-                    dx = GemmChain.run(F.linear, dy2c, wt).view(xc.shape).to(x_dt)
-            else:
-                dx = GemmChain.run(torch.mm, dy2, wc).view(xc.shape).to(x_dt)
-            if not ctx.needs_input_grad[1]:
-                dw = None
-            elif b_dt is None and _own_single(dy2c, x2c, False, False, torch.float32):
-                dw = hip_ops.gemm(dy2c, x2c, False, False, out_dtype=torch.float32).to(w_dt)
-            else:
-                dw = _tn_splitk(dy2c, x2c).to(w_dt)
+            dx = _linear_dgrad(dy2, dy2c, wc, b_dt is None).view(xc.shape).to(x_dt) if ctx.needs_input_grad[0] else None
+            dw = _linear_wgrad(dy2c, x2c, b_dt is None).to(w_dt) if ctx.needs_input_grad[1] else None
             db = dy2.sum(0, dtype=torch.float32).to(b_dt) if (b_dt is not None and ctx.needs_input_grad[2]) else None
         return dx, dw, db
+
+
+def _large_dgrad_nt(dy2c):
+    """The input gradient as an "NT" product with a transposed 16-bit copy of the weight?"""
+    return LARGE_DGRAD_NT and dy2c.is_cuda and dy2c.shape[0] >= LARGE_MIN_ROWS and dy2c.dtype in (torch.bfloat16, torch.float16)
+
+
+def _linear_dgrad(dy2, dy2c, wc, no_bias):
+    """dx [M, K] = dy2 [M, N] @ wc [N, K] of a projection (dy2c: dy2 made contiguous)."""
+    if no_bias and _own_single(dy2c, wc, True, False):
+        return hip_ops.gemm(dy2c, wc, True, False)
+    if _large_dgrad_nt(dy2c):
+        # dx = dy W as an "NT" product with a transposed 16-bit copy of the weight (a few MB, one small launch): both
+        # operands then have the contraction index contiguous.  Measured at M = 100 352 (tools/bench_gemm_large.py): the
+        # library's NN form 217 / 148 us (in_proj / out_proj) against 198 / 125 us for its NT form and 223 / 108 us for K12.
+        wt = wc.t().contiguous()
+        if _own_large(dy2c, wt):
+            return hip_ops.gemm_large(dy2c, wt)
+        return GemmChain.run(F.linear, dy2c, wt)
+    return GemmChain.run(torch.mm, dy2, wc)
+
+
+def _linear_wgrad(dy2c, x2c, no_bias):
+    """dW [N, K] fp32 = dy2c^T @ x2c."""
+    if no_bias and _own_single(dy2c, x2c, False, False, torch.float32):
+        return hip_ops.gemm(dy2c, x2c, False, False, out_dtype=torch.float32)
+    return _tn_splitk(dy2c, x2c)
 
 
 def linear_splitk(x, weight, bias=None):
@@ -465,10 +473,13 @@ class _SpiralSSMFn(torch.autograd.Function):
         return hip_ops.both if G == 2 else (lambda fn: (fn(0),))
 
     @staticmethod
-    def forward(ctx, grad_on, out_index, merge, G, *ops):
+    def forward(ctx, grad_on, out_index, merge, G, defer, *ops):
         """out_index (default: scan_index): row of the per-direction output that step l's result is written to -- the
         baseline blocks need a scatter that is not the gather's inverse (ViM, block/mamba.py:362-367).  merge=False returns
-        the per-direction outputs [ndir, B, L, Din] instead of their sum.  Returns a tuple of G outputs."""
+        the per-direction outputs [ndir, B, L, Din] instead of their sum.  Returns a tuple of G outputs.
+        defer (a _GateDefer or None; one mixer): the caller offers to run the hoisted gate's backward inside out_proj's input
+        gradient (_GatedOutProjFn).  Taken when the gate is hoisted and a backward will run: the outputs are then (y, pre), y not
+        differentiable, and the gradient that arrives for `pre` IS g = dy * silu(z)."""
         xz, idx, cw, cb, Wx, Wdt, bias, A, Dk = (ops[i * G:(i + 1) * G] for i in range(_SpiralSSMFn.NFIELD))
         stage, each = _SpiralSSMFn._stage(G), range(G)
         Bsz, L, D2 = xz[0].shape
@@ -525,6 +536,12 @@ class _SpiralSSMFn(torch.autograd.Function):
             stage(lambda g: hip_ops.token_merge(ydir[g].view(ndir, Bsz, L, Din), gate=xz[g][..., Din:],
                                                 pre_out=None if pre is None else pre[g], out=y[g]))
             out = tuple(y)
+            if defer is not None:
+                defer.taken = G == 1 and pre is not None
+                if defer.taken:
+                    out = (y[0], pre[0])
+                    ctx.mark_non_differentiable(y[0])
+                    ctx.set_materialize_grads(False)          # (no zero-filled gradient for y)
         elif not merge:
             out = tuple(t.view(ndir, Bsz, L, Din) for t in ydir)
         else:
@@ -533,6 +550,7 @@ class _SpiralSSMFn(torch.autograd.Function):
             ctx.save_for_backward(*xz, *idx, *oidx, *cw, *cb, *bias, *A, *Dk, *xc, *x_dbl, *delta, *ckpt,
                                   *((None,) * G if pre is None else pre), Wx_c, Wdt_c)
             ctx.meta = (G, merge, hoist, act, Wx[0].dtype, Wdt[0].dtype)
+            ctx.defer = defer if (defer is not None and defer.taken) else None
         return out
 
     @staticmethod
@@ -548,14 +566,22 @@ class _SpiralSSMFn(torch.autograd.Function):
         R, N = Wdt_c.shape[2], A[0].shape[1]
         S, M = ndir * Bsz, ndir * Bsz * L
         dt_, dev = xz[0].dtype, xz[0].device
-        dy = [t.contiguous().to(dt_) for t in dys]
-        if not merge:
-            dy = [t.view(S, L, Din) for t in dy]           # one gradient per direction
-        dxz = torch.empty((G, Bsz, L, D2), dtype=dt_, device=dev)
+        defer = ctx.defer
+        if defer is not None:
+            # out_proj's backward has run the gate's backward: dys[1] is g, and the z half of d(xz) is written in its buffer
+            assert dys[1] is not None and defer.dxz is not None, "the deferred gate backward did not run"
+            gy, dxz, defer.dxz = [dys[1].contiguous().to(dt_)], defer.dxz, None
+        else:
+            dy = [t.contiguous().to(dt_) for t in dys]
+            if not merge:
+                dy = [t.view(S, L, Din) for t in dy]       # one gradient per direction
+            dxz = torch.empty((G, Bsz, L, D2), dtype=dt_, device=dev)
         dx_dbl = torch.empty((G, M, R + 2 * N), dtype=dt_, device=dev)
         du = torch.empty((G, S, L, Din), dtype=dt_, device=dev)
         xd3 = [t.view(S, L, R + 2 * N) for t in x_dbl]
-        if hoist:
+        if defer is not None:
+            pass
+        elif hoist:
             # the gate's backward once per token: g = dy * silu(z) is what the three directions read as their output gradient,
             # dz = dy * pre * silu'(z) goes straight into the z half of d(xz) (no dz slabs, no 3-slab merge)
             gy = stage(lambda g: hip_ops.gate_bwd(dy[g], xz[g][..., Din:], pre[g], dz_out=dxz[g][..., Din:])[0])
@@ -603,7 +629,7 @@ class _SpiralSSMFn(torch.autograd.Function):
                  [t.to(wx_dt) for t in dWx], [t.to(wdt_dt) for t in dWdt],
                  [res[g][7].to(bias[g].dtype) for g in each], [res[g][5].to(A[g].dtype) for g in each],
                  [res[g][6].to(Dk[g].dtype) for g in each])
-        return (None, None, None, None) + tuple(t for field in grads for t in field)
+        return (None, None, None, None, None) + tuple(t for field in grads for t in field)
 
 
 def spiral_ssm_pair_supported(Bsz, L, dtype, mix0, mix1):
@@ -629,7 +655,7 @@ def spiral_ssm_pair(xz0, xz1, mix0, mix1, A0, A1):
     """The fused 3-direction operator (spiral_ssm) for the two mixers of a block in one set of launches."""
     per = lambda f: (f(mix0), f(mix1))
     with torch.autocast(device_type="cuda", enabled=False):
-        return _SpiralSSMFn.apply(torch.is_grad_enabled(), None, True, 2, xz0, xz1, *per(lambda m: m.scan_index),
+        return _SpiralSSMFn.apply(torch.is_grad_enabled(), None, True, 2, None, xz0, xz1, *per(lambda m: m.scan_index),
                                   *per(lambda m: m.conv1d.weight), *per(lambda m: m.conv1d.bias), *per(lambda m: m.x_proj.weight),
                                   *per(lambda m: m.dt_proj.weight), *per(lambda m: m.dt_proj.bias.float()), A0.float(), A1.float(),
                                   *per(lambda m: m.D.float()))
@@ -795,8 +821,100 @@ def spiral_ssm(xz, conv_w, conv_b, x_proj_w, dt_proj_w, dt_proj_b, A, Dskip, sca
     out_index / merge: see _SpiralSSMFn.forward.  Returns y [B, L, Din] (or [ndir, B, L, Din]); the caller applies out_proj.
     """
     with torch.autocast(device_type="cuda", enabled=False):
-        return _SpiralSSMFn.apply(torch.is_grad_enabled(), out_index, merge, 1, xz, scan_index, conv_w, conv_b, x_proj_w, dt_proj_w,
+        return _SpiralSSMFn.apply(torch.is_grad_enabled(), out_index, merge, 1, None, xz, scan_index, conv_w, conv_b, x_proj_w, dt_proj_w,
                                   dt_proj_b.float(), A.float(), Dskip.float())[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# The gate's backward inside out_proj's input gradient (csrc/gemm_large.hip, dm_gemm_large with gate_z set)
+# ------------------------------------------------------------------------------------------------
+# Backward of "merge output -> out_proj" at large batch: K12 forms dy = d(out) W tile by tile and the hoisted gate's backward reads
+# it back at once (dm_gate_bwd: dy, z, pre -> g, dz).  With the gate applied in K12's epilogue dy never reaches memory (205 MB written
+# and read per mixer at the bench batch, and one launch).  out_proj's weight gradient is d(out)^T y -- the gradient that ARRIVES and
+# the saved merge output -- and out_proj has no bias here, so nothing else reads dy.  Taken when the gate is hoisted, the tensors are
+# 16-bit and the input gradient would go to K12 as an NT product anyway; DIFFMA_GATE_IN_DGRAD=0 (hip_ops.GATE_IN_DGRAD) keeps the
+# two launches.
+class _GateDefer:
+    """What the two autograd nodes of one mixer share: `taken` (set by _SpiralSSMFn.forward) and the d(xz) buffer, which
+    _GatedOutProjFn.backward allocates (and writes the z half of) and _SpiralSSMFn.backward completes and returns -- one owner at a time."""
+    __slots__ = ("taken", "dxz")
+
+    def __init__(self):
+        self.taken, self.dxz = False, None
+
+
+def _gate_in_dgrad_rule(on_gpu, dtype, autocast_dtype, contiguous, wants_grad, xz_shape, w_shape):
+    """The routing rule on plain values (so that it can be checked without a device): the switches; 16-bit activations that autocast
+    would not change; a backward to come; and the shape test of _linear_dgrad for dy [M, K = d_model] @ wt [N = d_inner, K]^T -- at
+    least LARGE_MIN_ROWS rows (above the small-launch kernel's range), K12's column rule, a shape K12 takes."""
+    if not (hip_ops.GATE_IN_DGRAD and HOIST_GATE and LARGE_DGRAD_NT and hip_ops.GEMM_LARGE):
+        return False
+    if not (on_gpu and len(xz_shape) == 3 and contiguous and wants_grad and dtype in (torch.bfloat16, torch.float16)):
+        return False
+    if autocast_dtype is not None and autocast_dtype != dtype:
+        return False
+    M, N, K = xz_shape[0] * xz_shape[1], w_shape[1], w_shape[0]
+    if N * 2 != xz_shape[2] or M < LARGE_MIN_ROWS or N < LARGE_MIN_COLS or (N < 1024 and K > LARGE_MAX_K_NARROW) or M <= PAIR_OWN_MAX_ROWS:
+        return False
+    code = {torch.bfloat16: _lib.DM_BF16, torch.float16: _lib.DM_F16}[dtype]
+    return bool(_lib.load().dm_gemm_large_gated_supported(M, N, K, code))
+
+
+def gate_in_dgrad_wanted(xz, weight):
+    """Would out_proj's input gradient go to K12 as an NT product, with a hoisted gate in front of it?"""
+    ac = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None
+    return _gate_in_dgrad_rule(xz.is_cuda, xz.dtype, ac, xz.is_contiguous(), torch.is_grad_enabled() and xz.requires_grad,
+                               tuple(xz.shape), tuple(weight.shape))
+
+
+class _GatedOutProjFn(torch.autograd.Function):
+    """out = y W^T for the bias-free out_proj behind a mixer whose gate is hoisted (y = pre * silu(z), both from _SpiralSSMFn), with
+    the gate's backward in the input gradient: the gradient returned for `pre` is g = (d(out) W) * silu(z), and dz is written into
+    the z half of the d(xz) buffer that `defer` hands to _SpiralSSMFn.backward.  y is a value here, not a differentiable input."""
+
+    @staticmethod
+    def forward(ctx, y, pre, xz, weight, defer):
+        wc = cast_weight(weight, y.dtype)
+        ctx.save_for_backward(y, pre, xz, wc)
+        ctx.defer, ctx.w_dt = defer, weight.dtype
+        y2 = y.reshape(-1, y.shape[-1])
+        if _own_large(y2, wc):
+            return hip_ops.gemm_large(y2, wc).view(*y.shape[:-1], wc.shape[0])
+        return GemmChain.run(F.linear, y, wc, None)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, pre, xz, wc = ctx.saved_tensors
+        Bsz, L, D2 = xz.shape
+        Din = D2 // 2
+        with torch.autocast(device_type=y.device.type, enabled=False):
+            dy2 = dout.reshape(-1, dout.shape[-1])
+            if dy2.dtype != y.dtype:
+                dy2 = dy2.to(y.dtype)
+            dy2c = dy2.contiguous()
+            dxz = torch.empty((1, Bsz, L, D2), dtype=xz.dtype, device=xz.device)
+            z2, dz2, pre2 = xz.view(-1, D2)[:, Din:], dxz.view(-1, D2)[:, Din:], pre.view(-1, Din)
+            wt = wc.t().contiguous()
+            if hip_ops.gemm_large_gated_supported(dy2c, wt, z2, pre2, dz2):
+                g = hip_ops.gemm_large_gated(dy2c, wt, z2, pre2, dz2).view(Bsz, L, Din)
+            else:       # (a gradient layout that K12 does not take: the two launches, into the same buffers)
+                dy = _linear_dgrad(dy2, dy2c, wc, True).view(Bsz, L, Din)
+                g = hip_ops.gate_bwd(dy, xz[..., Din:], pre, dz_out=dxz[0][..., Din:])[0]
+            dw = _linear_wgrad(dy2c, y.reshape(-1, Din).contiguous(), True).to(ctx.w_dt) if ctx.needs_input_grad[3] else None
+            ctx.defer.dxz = dxz
+        return None, g, None, dw, None
+
+
+def spiral_ssm_out_proj(xz, conv_w, conv_b, x_proj_w, dt_proj_w, dt_proj_b, A, Dskip, scan_index, out_proj_w):
+    """linear_splitk(spiral_ssm(xz, ...), out_proj_w) for the bias-free out_proj of the spiral mixer where gate_in_dgrad_wanted says
+    so: the gate's backward runs inside out_proj's input gradient (above)."""
+    defer = _GateDefer()                 # (the caller asked gate_in_dgrad_wanted)
+    with torch.autocast(device_type="cuda", enabled=False):
+        outs = _SpiralSSMFn.apply(torch.is_grad_enabled(), None, True, 1, defer, xz, scan_index, conv_w, conv_b, x_proj_w, dt_proj_w,
+                                  dt_proj_b.float(), A.float(), Dskip.float())
+    if defer.taken:
+        return _GatedOutProjFn.apply(outs[0], outs[1], xz, out_proj_w, defer)
+    return linear_splitk(outs[0].to(xz.dtype), out_proj_w, None)
 
 
 _CONSTS = {}

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 32
+#define DM_ABI_VERSION 33
 
 typedef enum {
     DM_OK = 0,
@@ -760,6 +760,11 @@ typedef struct {
     const void *a, *b;
     void *c;
     int64_t lda, ldb, ldc;   /* row strides of the STORED matrices, elements */
+    /* ABI 33, dm_gemm_large only (dm_gemm and dm_gemm_n refuse a non-NULL gate_z): the gated epilogue described below at
+     * dm_gemm_large.  c / ldc are then the dy slice of the remainder rows (c may be NULL when dm_gemm_large_tail_rows(P, Q) is 0). */
+    const void *gate_z, *gate_pre;
+    void *gate_g, *gate_dz;
+    int64_t gate_ldz, gate_ldp, gate_ldg, gate_lddz;
 } dm_gemm_args;
 
 int dm_gemm(const dm_gemm_args *args, void *stream);
@@ -775,6 +780,21 @@ int dm_gemm_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, int ab_d
  * ---------------------------------------------------------------------------------------------- */
 int dm_gemm_large(const dm_gemm_args *args, void *stream);
 int dm_gemm_large_supported(int P, int Q, int Kc, int a_kmajor, int b_kmajor, int ab_dtype, int c_dtype);
+
+/* ------------------------------------------------------------------------------------------------
+ * K12 with the hoisted gate's backward in its epilogue (ABI 33): dm_gemm_large with gate_z != NULL.  The product is the input
+ * gradient of out_proj, dy[P][Q] = A[P][Kc] * B[Q][Kc]^T (A = d(out), B = the transposed 16-bit weight copy); what the kernel stores
+ * is dm_gate_bwd of it,   gate_g = dy * silu(gate_z),   gate_dz = dy * gate_pre * silu'(gate_z),   with dy rounded to the I/O dtype
+ * first -- what dm_gemm_large followed by dm_gate_bwd writes, without dy's round trip through memory.  dy itself is NOT written.
+ * gate_z, gate_pre, gate_g, gate_dz: [P][Q] row-major; dz takes the row stride of z (gate_lddz == gate_ldz: the z halves of xz and
+ * d(xz), stride 2 Q) and g that of pre (gate_ldg == gate_ldp), anything else is DM_ERR_LAYOUT.  fp32 is DM_ERR_DTYPE; a shape
+ * dm_gemm_large does not take, c_dtype != ab_dtype or accumulate is DM_ERR_ARG (dm_gemm_large_gated_supported answers for a shape).
+ * Every row stride % 8 == 0, every tensor 16-byte aligned and below 2 GB.
+ * The rows that dm_gemm_large hands to dm_gemm -- dm_gemm_large_tail_rows(P, Q) of them, the last ones -- keep the two launches
+ * (dm_gemm into c, dm_gate_bwd on it): c [tail rows][Q] (row stride ldc) is scratch of the caller's, NULL when there are none.
+ * ---------------------------------------------------------------------------------------------- */
+int dm_gemm_large_gated_supported(int P, int Q, int Kc, int ab_dtype);
+int dm_gemm_large_tail_rows(int P, int Q);
 
 /* ------------------------------------------------------------------------------------------------
  * Several congruent launches in one (ABI 25).
