@@ -10,6 +10,7 @@
 //     DDIM:  eps'   = (sqrt(1/abar_t) * x - x0) / sqrt(1/abar_t - 1)
 //            sigma  = eta * sqrt((1 - abar_prev) / (1 - abar_t)) * sqrt(1 - abar_t / abar_prev)
 //            sample = x0 * sqrt(abar_prev) + sqrt(1 - abar_prev - sigma^2) * eps' + [t != 0] * sigma * noise
+// Every expression is fp32 on the fp32 value of the model output: no intermediate is rounded to the model output's dtype.
 // The per-timestep coefficients come from the caller's device-resident fp32 table [nrows][T] (row numbers in the args); t is
 // read per batch element, so one launch serves a batch of mixed timesteps.  Pure HBM work: 5 reads + 2 writes per element.
 #include "dm_common.h"
@@ -24,6 +25,12 @@ __global__ __launch_bounds__(256) void diffusion_step_kernel(const dm_diffusion_
         const int b = (int)(e / per);
         const int64_t r = e - (int64_t)b * per;
         const int64_t t = p.t[b];
+        // a timestep outside [0, T) reads no table entry: the sample comes back NaN, as in q_sample_kernel (precondition in diffma_hip.h)
+        if ((uint64_t)t >= (uint64_t)p.T) {
+            p.sample[e] = __builtin_nanf("");
+            if (p.pred_xstart) p.pred_xstart[e] = __builtin_nanf("");
+            continue;
+        }
         const float* tab = p.tables + t;
         const float c_recip = tab[(int64_t)p.row_sqrt_recip_ac * p.T], c_recipm1 = tab[(int64_t)p.row_sqrt_recipm1_ac * p.T];
         const float min_log = tab[(int64_t)p.row_post_logvar * p.T], max_log = tab[(int64_t)p.row_log_betas * p.T];

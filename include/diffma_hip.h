@@ -722,6 +722,10 @@ int dm_ssd_bwd_wide_supported(int seqlen, int headdim, int dstate, int io_dtype)
  * t: int64 [batch].  tables: fp32 [nrows][T], the caller's per-timestep coefficient rows; the row_* fields name the rows of
  * log(posterior variance, clipped), log(beta), sqrt(1/abar), sqrt(1/abar - 1), posterior mean coefficients 1 and 2, abar and
  * abar_prev.  mode 0 = ancestral (DDPM) step, 1 = DDIM step with `eta`.
+ * PRECONDITION 0 <= t[b] < T: a timestep outside the range (a respaced / unspaced mix-up) reads no table entry; that sample's
+ * `sample` and `pred_xstart` come back NaN, as dm_q_sample and dm_training_loss treat it.
+ * The contract is the formula of csrc/diffusion_step.hip evaluated on the fp32 value of each model output element: unlike
+ * dm_training_loss, (v + 1) / 2 and 1 - frac are NOT rounded to the model output's dtype.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t batch, channels, hw, T;
