@@ -1255,6 +1255,11 @@ def ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_
     """x: [S, L, H*64] view, Bm / Cm: [S, L, N] views, N = d_state in 16 / 32 / 64 / 128 (after the conv, per gathered sequence);
     dt_tok: [B, L, H] and z: [B, L, H*64] in token order; A_h, D_h, dt_bias_h: [H] fp32.  Returns the gated output [S, L, H*64] with
     step l at row out_row_index[dir][l]."""
+    return _ssd_fwd_launch("dm_ssd_fwd", x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index, out_row_index, batch_per_dir, out)
+
+
+def _ssd_fwd_launch(entry, x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index, out_row_index, batch_per_dir, out):
+    """dm_ssd_fwd and dm_ssd_fwd_chunked take the same struct."""
     _require_gpu(x, Bm, Cm, dt_tok, z)
     S, L, Din = x.shape
     H = A_h.shape[0]
@@ -1278,8 +1283,45 @@ def ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_
         a.z_ss, a.z_sl = z.stride(0), z.stride(1)
     a.o_ss, a.o_sl = out.stride(0), out.stride(1)
     es = x.element_size()
-    _launch("dm_ssd_fwd", a, x, (3 if z is not None else 2) * S * L * Din * es + 2 * S * L * N * es)
+    _launch(entry, a, x, (3 if z is not None else 2) * S * L * Din * es + 2 * S * L * N * es)
     return out
+
+
+# The same operator past one chunk (csrc/ssd_chunked.hip): forward only, 1 <= L <= 1024, the sequence walked in chunks of
+# dm_ssd_fwd_chunk_len(d_state) tokens (128, 128, 96, 64 at d_state 16, 32, 64, 128) with the state carried in fp32 registers.  A
+# no-grad Mamba-2 call that dm_ssd_fwd turns down only for its length (L > 224: the 256- and 512-pixel image sizes) comes here instead
+# of the A-shared scan; calls that need gradients stay on the scan pair.  DIFFMA_SSD_CHUNKED=0 returns those calls to the scan.
+SSD_CHUNKED = os.environ.get("DIFFMA_SSD_CHUNKED", "1") == "1"
+# The widths routed by default, by the rule above SSD_FWD_WIDTHS: 1.1 x or more against the A-shared scan forward at every launch size
+# and both lengths; a width left out stays reachable through ssd_fwd_chunked().  All four qualify (worst 1.42 x: d_state 16, L 1024,
+# nseq 192).  DiffMa-XL/2 mixer shape (16 heads x 64, bf16, three directions), ssd_fwd_chunked() vs the scan in us at nseq 3 / 24 / 192,
+# L = 256 | L = 1024 (profiles/ssd_fwd_chunked.json, one MI355X, one session, alternating windows, spread <= 0.4 %):
+#     d_state  16      31 vs    75     33 vs    91    109 vs   179  |    116 vs   256    128 vs   291    449 vs   636      Q 128, 247 VGPRs, 43 KB LDS
+#     d_state  32      32 vs   127     34 vs   146    110 vs   327  |    121 vs   467    132 vs   517    460 vs  1223      Q 128, 246 VGPRs, 51 KB LDS
+#     d_state  64      35 vs   108     37 vs   145    121 vs   386  |    134 vs   389    145 vs   500    499 vs  1486      Q  96, 248 VGPRs, 58 KB LDS
+#     d_state 128      39 vs   109     41 vs   188    135 vs  1102  |    155 vs   390    165 vs   668    555 vs  4272      Q  64, 256 VGPRs, 65 KB LDS
+# One 8-wave workgroup per (sequence, 4 heads), two waves per SIMD, at every width; no instantiation spills, no scratch (bf16 figures;
+# fp16 needs 4 - 21 registers fewer; tools/kernel_regs.sh ssd_chunked).
+SSD_FWD_CHUNKED_WIDTHS = (16, 32, 64, 128)
+
+
+def ssd_fwd_chunked_supported(x, L, headdim, dstate, views=(), gate=None):
+    """As ssd_fwd_supported for dm_ssd_fwd_chunked; the gate's rows need 4-byte boundaries only at every width."""
+    if not (SSD_MFMA and SSD_CHUNKED and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)):
+        return False
+    if int(dstate) not in SSD_FWD_CHUNKED_WIDTHS:
+        return False
+    for v in views:
+        if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
+            return False
+    if gate is not None and (gate.data_ptr() % 4 or gate.stride(-1) != 1 or any(st % 2 for st in gate.stride()[:-1])):
+        return False
+    return bool(_lib.load().dm_ssd_fwd_chunked_supported(int(L), int(headdim), int(dstate), dtype_code(x)))
+
+
+def ssd_fwd_chunked(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, *, z_row_index=None, out_row_index=None, batch_per_dir=0, out=None):
+    """Operands and result as ssd_fwd, for 1 <= L <= 1024 (csrc/ssd_chunked.hip)."""
+    return _ssd_fwd_launch("dm_ssd_fwd_chunked", x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index, out_row_index, batch_per_dir, out)
 
 
 # Backward twin (csrc/ssd_bwd.hip): one workgroup per (sequence, head) recomputes the score tiles, nothing is saved by the

@@ -695,6 +695,13 @@ class _SpiralSSDFn(torch.autograd.Function):
                 ctx.save_for_backward(zxbcdt, conv_w, conv_b, xBC, ydir, rstd, norm_w, scan_index, A_h, D_h, dt_bias_h)
                 ctx.meta = (Din, N, H, P, eps, dt_bias_h.dtype, A_h.dtype, D_h.dtype)
             return out
+        if (not need_grad and hip_ops.ssd_fwd_supported(xBC, 1, P, N, views=(x, Bm, Cm), gate=z)      # (L = 1: everything but the length)
+                and hip_ops.ssd_fwd_chunked_supported(xBC, L, P, N, views=(x, Bm, Cm), gate=z)):
+            # turned down above for its length only (L > 224) and no gradients needed: the chunked matrix-pipe forward
+            # (csrc/ssd_chunked.hip) instead of the scan; a call that needs gradients goes on to the scan pair below
+            ydir = hip_ops.ssd_fwd_chunked(x, Bm, Cm, dt_tok, z, A_h, D_h, dt_bias_h, z_row_index=scan_index, out_row_index=scan_index,
+                                           batch_per_dir=Bsz)
+            return _SpiralSSDFn._norm_merge(ydir, norm_w, eps, ndir, Bsz, L, Din)[0]
         # dt is produced per token and per head: gather its rows per direction, broadcast head -> channels
         idx64 = scan_index.long()
         dt_g = torch.stack([dt_tok[:, idx64[k]] for k in range(ndir)])                                            # [ndir, B, L, H]
@@ -786,15 +793,15 @@ def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias
                                      ngroups=1, norm_before_gate=True):
     """Drop-in for mamba_ssm's Mamba-2 fused operator with the keyword usage of block/mamba2.py:392-410.
 
-    zxbcdt: (B, L, 2*dim + 2*ngroups*N + H), columns [z | x | B | C | dt].  Single chunk (chunk_size >= L, the only case
-    DiffMa reaches: chunk_size 256, L <= 196), scalar D per head, ngroups 1.  Returns (B, L, d_model)."""
+    zxbcdt: (B, L, 2*dim + 2*ngroups*N + H), columns [z | x | B | C | dt].  Scalar D per head, ngroups 1.  Returns (B, L, d_model).
+    The result does not depend on chunk_size: up to L = 224 the matrix-pipe kernels treat the sequence as one chunk, past that a
+    no-grad call runs dm_ssd_fwd_chunked with the kernel's own chunk length (hip_ops.ssd_fwd_chunked), and every other call takes
+    the A-shared scan, which has no chunks at all."""
     if initial_states is not None or seq_idx is not None or return_final_states or ngroups != 1 or headdim is None:
         raise NotImplementedError("only the call pattern of block/mamba2.py:392-410 is built (ngroups=1, scalar D, no states)")
     if activation not in ("silu", "swish") or dt_limit != (0.0, float("inf")):
         raise NotImplementedError("activation must be silu and dt_limit unbounded")
     Bsz, L, _ = zxbcdt.shape
-    if chunk_size < L:
-        raise NotImplementedError("multi-chunk SSD (chunk_size < seqlen) is never reached by DiffMa")
     if rmsnorm_weight is not None and norm_before_gate:
         raise NotImplementedError("norm_before_gate=True (norm, then gate) is not wired; DiffMa uses norm_before_gate=False (block/mamba2.py:349)")
     H = D.shape[0]
@@ -805,6 +812,7 @@ def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias
     # ONE autograd node, the same one the Mamba2 module runs with three directions: conv (K3), the single-chunk SSD core on the
     # matrix pipe (dm_ssd_fwd / dm_ssd_bwd) when the shape allows it -- 16-bit I/O, headdim 64, 16-byte aligned rows, d_state 16 (or a
     # wide state of hip_ops.SSD_FWD_WIDTHS: without gradients, or with hip_ops.SSD_MFMA_BWD_WIDE on, dm_ssd_bwd_wide) --
+    # past L = 224 without gradients the chunked forward (dm_ssd_fwd_chunked, hip_ops.SSD_FWD_CHUNKED_WIDTHS),
     # else the A-shared selective scan, then the gated RMSNorm (dm_rmsnorm_merge_*, one slab) when rmsnorm_weight is given.
     ident = _const("ident", L, zxbcdt.device)
     y = spiral_ssd(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, rmsnorm_weight, rmsnorm_eps, ident, ident, dim, N)

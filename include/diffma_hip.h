@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 33
+#define DM_ABI_VERSION 34
 
 typedef enum {
     DM_OK = 0,
@@ -666,6 +666,26 @@ typedef struct {
 
 int dm_ssd_fwd(const dm_ssd_fwd_args *args, void *stream);
 int dm_ssd_fwd_supported(int seqlen, int headdim, int dstate, int io_dtype);
+
+/* ------------------------------------------------------------------------------------------------
+ * The same operator past one chunk (ABI 34): forward only, the no-grad regime of sampling and EMA evaluation at the 256- and
+ * 512-pixel image sizes (256 and 1024 tokens at patch 2).  Same struct, same operands, same result as dm_ssd_fwd; the sequence is
+ * walked in chunks of Q = dm_ssd_fwd_chunk_len(dstate) tokens (128, 128, 96, 64 at d_state 16, 32, 64, 128) by one workgroup per
+ * (sequence, 4 heads), the SSD state carried from chunk to chunk in fp32:
+ *     y_l    = [the dual form above over the keys of l's own chunk] + exp(s_l) sum_n C_l[n] h[n][p] + D[h] x_l
+ *     h_next = exp(s_end) h + sum_{i in chunk} exp(s_end - s_i) dt_i B_i[n] x_i[p]          (s: chunk-local prefix sums)
+ * Limits: 16-bit I/O, headdim 64, d_state 16 / 32 / 64 / 128, 1 <= seqlen <= DM_SSD_FWD_CHUNKED_MAXL (a short sequence is one
+ * chunk); x / B / C / out rows on 16-byte boundaries as for dm_ssd_fwd, z rows on 4-byte boundaries at every width.  Up to 65 KB of
+ * dynamic LDS (d_state 128).
+ * Roundings to the I/O dtype: inside a chunk those of the wide dm_ssd_fwd (the score tile once, B and C as given); a pair whose key
+ * lies in an earlier chunk pays two -- dt_i exp(s_end - s_i) x_i where it enters the state update, and the carried state where a
+ * query tile reads it (once, however many chunks it crossed) -- and the output is rounded once.
+ * The result does not depend on any chunk_size of the caller.  dm_ssd_fwd_supported() is unchanged (seqlen <= 224).
+ * ---------------------------------------------------------------------------------------------- */
+#define DM_SSD_FWD_CHUNKED_MAXL 1024
+int dm_ssd_fwd_chunked(const dm_ssd_fwd_args *args, void *stream);
+int dm_ssd_fwd_chunked_supported(int seqlen, int headdim, int dstate, int io_dtype);
+int dm_ssd_fwd_chunk_len(int dstate);      /* Q; <= 0 if the width is not served */
 
 /* ------------------------------------------------------------------------------------------------
  * Backward twin of dm_ssd_fwd (same operator, same operands; SURVEY.md A.2, reference call block/mamba2.py:392-410 under

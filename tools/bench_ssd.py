@@ -1,8 +1,10 @@
 """Mamba-2 SSD forward on the matrix pipe (K6) against the A-shared scan at the DiffMa-XL/2 --use-mamba2 shape -- run on the GPU box.
-    tools/bench_ssd.py [--d-state N] [batch ...]      N in 16 (default) / 32 / 64 / 128
+    tools/bench_ssd.py [--d-state N] [--seqlen L] [batch ...]      N in 16 (default) / 32 / 64 / 128, L = 196 (default) .. 1024
 Both pairs are timed at every width: dm_ssd_fwd against the A-shared scan forward, and the matrix-pipe backward (dm_ssd_bwd at 16,
 dm_ssd_bwd_wide at 32 / 64 / 128, called through hip_ops.ssd_bwd whatever the routing switches say) against the A-shared scan
-backward.  The backward pair alternates three windows of at least 0.1 s each and reports the medians and the spread."""
+backward.  The backward pair alternates three windows of at least 0.1 s each and reports the medians and the spread.
+Past L = 224 (--seqlen 256, --seqlen 1024: the 256- and 512-pixel image sizes) the forward pair is dm_ssd_fwd_chunked against the A-shared
+scan forward, timed the same way (alternating windows, medians, spread); there is no matrix-pipe backward at those lengths."""
 import argparse, os, sys, json
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,9 +13,11 @@ from diffma_amd import hip_ops  # noqa: E402
 dev = torch.device("cuda", 0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--d-state", type=int, default=16)
+ap.add_argument("--seqlen", type=int, default=196)
 ap.add_argument("batches", nargs="*", type=int, default=[8, 64, 256])
 args = ap.parse_args()
-L, H, P, N = 196, 16, 64, args.d_state
+L, H, P, N = args.seqlen, 16, 64, args.d_state
+CHUNKED = L > 224
 Din = H * P
 dt_ = torch.bfloat16
 
@@ -43,7 +47,7 @@ for B in args.batches:
     out = torch.empty(S, L, Din, device=dev, dtype=dt_)
 
     def mfma():
-        return hip_ops.ssd_fwd(x, Bm, Cm, dt_tok, z, A_h, D_h, b_h, z_row_index=idx, out_row_index=idx, batch_per_dir=B, out=out)
+        return (hip_ops.ssd_fwd_chunked if CHUNKED else hip_ops.ssd_fwd)(x, Bm, Cm, dt_tok, z, A_h, D_h, b_h, z_row_index=idx, out_row_index=idx, batch_per_dir=B, out=out)
 
     A = A_h.repeat_interleave(P)[:, None].expand(Din, N).contiguous()
     Dp, bp = D_h.repeat_interleave(P), b_h.repeat_interleave(P)
@@ -88,6 +92,20 @@ for B in args.batches:
     a = mfma().float().clone()
     b = scan().float()
     nb = 3 * S * L * Din * 2
+    if CHUNKED:
+        iters = lambda fn: max(10, int(1e5 / timeit(fn, 5)))                   # a window of 0.1 s or more
+        n_m, n_s = iters(mfma), iters(scan)
+        t_mf, t_sf = [], []
+        for _ in range(3):                                                     # alternate the two: other work shares the host
+            t_mf.append(timeit(mfma, n_m))
+            t_sf.append(timeit(scan, n_s))
+        med = lambda v: sorted(v)[1]
+        t_m, t_s = med(t_mf), med(t_sf)
+        print(json.dumps(dict(d_state=N, seqlen=L, batch=B, nseq=S, ssd_chunked_us=round(t_m, 1), a_shared_scan_us=round(t_s, 1), scan_over_chunked=round(t_s / t_m, 2),
+                              spread_chunked=round((max(t_mf) - min(t_mf)) / t_m, 3), spread_scan=round((max(t_sf) - min(t_sf)) / t_s, 3),
+                              chunk_len=hip_ops._lib.load().dm_ssd_fwd_chunk_len(N), chunked_GBps=round(nb / t_m / 1e3, 1),
+                              max_abs_diff=float((a - b).abs().max()), scale=float(b.abs().max()))), flush=True)
+        continue
     t_m, t_s = timeit(mfma), timeit(scan)
     res = dict(d_state=N, batch=B, nseq=S, ssd_mfma_us=round(t_m, 1), a_shared_scan_us=round(t_s, 1), scan_over_mfma=round(t_s / t_m, 2),
                mfma_GBps=round(nb / t_m / 1e3, 1), max_abs_diff=float((a - b).abs().max()), scale=float(b.abs().max()))
