@@ -245,6 +245,32 @@ def _variant_flag(variant):
     return {"sequential": DM_FLAG_SCAN_SEQUENTIAL, "chunked": DM_FLAG_SCAN_CHUNKED}[variant]
 
 
+# The chunk-parallel forward past one segment (csrc/scan_fwd_chunked.h: 196 < L <= 1024, the 256- and 512-pixel image sizes at
+# patch 2, walked in segments of 140 tokens).  The library takes it for small launches, by the routing rule above SSD_FWD_WIDTHS
+# (only where it reaches 1.1 x the sequential kernel): up to 512 channel-waves, 256 with checkpoints.  Kernel alone, bf16, dim 1024,
+# nseq 3 / 15 / 24: 63 -> 31, 67 -> 32, 71 -> 59 us at L 256 and 262 -> 116, 266 -> 121, 276 -> 232 us at L 1024; the graphed batch-1
+# denoiser call of DiffMa-L/2 4.20 -> 2.66 ms at 256 tokens and 10.55 -> 4.27 ms at 1024 (profiles/scan_fwd_chunked_long.json;
+# tools/scan_variants.py --forward-only --seqlen L).  The backward stays on the sequential kernel past 196 tokens.
+# DIFFMA_SCAN_CHUNKED_LONG=0 returns those forward launches to the sequential kernel (A/B runs, and the way back).
+SCAN_CHUNKED_LONG = os.environ.get("DIFFMA_SCAN_CHUNKED_LONG", "1") == "1"
+SCAN_CHUNKED_SEGMENT = 196          # tokens one segment holds: longer forward launches are the ones the switch above covers
+
+
+def _scan_fwd_variant_flag(L, variant):
+    """_variant_flag for a forward launch of L tokens: with SCAN_CHUNKED_LONG off, launches the library would choose for itself
+    (variant None) carry DM_FLAG_SCAN_SEQUENTIAL past one segment."""
+    if variant is None and not SCAN_CHUNKED_LONG and L > SCAN_CHUNKED_SEGMENT:
+        return DM_FLAG_SCAN_SEQUENTIAL
+    return _variant_flag(variant)
+
+
+def scan_fwd_segment(S, Dm, L, N, flags=0):
+    """Tokens per segment of the chunk-parallel forward that a launch [S, L, Dm] at d_state N with these flags takes (196 up to 196
+    tokens, 140 past that), or 0 where it takes the sequential kernel (dm_scan_fwd_launch_segment: sizes only, no device; a launch
+    without checkpoints -- one that writes them past 196 tokens is taken up to 256 channel-waves instead of 512)."""
+    return int(_lib.load().dm_scan_fwd_launch_segment(S, Dm, L, N, flags))
+
+
 def _scan_args(a, u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, delta_activated, z_row_index, out_row_index, batch_per_dir,
                ckpt, ckpt_every, ngroups, a_shared, variant, more_flags=0):
     """The flag word and the fields that dm_scan_fwd_args and dm_scan_bwd_args share.  A, D, delta_bias: fp32 contiguous (_f32c), held
@@ -308,7 +334,8 @@ def _scan_fwd_launch(u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, z_ro
     N = A.shape[1]
     A, D, delta_bias = _f32c(A), _f32c(D), _f32c(delta_bias)
     a = _scan_args(dm_scan_fwd_args(), u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, delta_activated, z_row_index, out_row_index,
-                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, variant, DM_FLAG_OUT_ACCUMULATE if accumulate else 0)
+                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, None,
+                   _scan_fwd_variant_flag(L, variant) | (DM_FLAG_OUT_ACCUMULATE if accumulate else 0))
     a.out, a.last_state = _ptr(out), _ptr(last_state)
     a.o_ss, a.o_sl, a.o_sd = out.stride()
     nbytes = scan_fwd_algorithmic_bytes(S, Dm, L, N, u.element_size(), Bm.element_size(), z is not None)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 34
+#define DM_ABI_VERSION 35
 
 typedef enum {
     DM_OK = 0,
@@ -53,8 +53,10 @@ enum {
                                    Mamba-2: the gated RMSNorm sits between the scan and the merge) instead of
                                    [batch_per_dir][row][d] shared by the directions  */
     DM_FLAG_SCAN_SEQUENTIAL = 16, /* scan fwd / bwd: take the sequential-in-time kernel whatever the launch size          */
-    DM_FLAG_SCAN_CHUNKED = 32,  /* scan fwd / bwd: take the chunk-parallel (two-pass) kernel where it is instantiated;
-                                   by default the library chooses by launch size (small launches are latency-bound)       */
+    DM_FLAG_SCAN_CHUNKED = 32,  /* scan fwd / bwd: take the chunk-parallel (two-pass) kernel where it is instantiated: the
+                                   forward for 56 < seqlen <= 1024 (past 196 tokens in segments, ABI 35), the backward up to
+                                   196 tokens (longer ones stay on the sequential kernel, which reads the same checkpoints).
+                                   By default the library chooses by launch size (small launches are latency-bound)       */
     DM_FLAG_OUT_ACCUMULATE = 64, /* scan fwd with row indices: out[s][out_row_index[l]] += y (read-add-store) instead of = y.
                                    The caller walks the directions of the CrossMerge (block/mamba.py:59-69) with one launch
                                    each into ONE token-order buffer: direction 0 stores, the others accumulate, and the
@@ -209,6 +211,16 @@ typedef struct {
 } dm_scan_fwd_args;
 
 int dm_selective_scan_fwd(const dm_scan_fwd_args *args, void *stream);
+/* Host-only query (ABI 35), the forward twin of dm_scan_bwd_launch_group_channels: which kernel a forward launch of this size takes.
+ * 0: the sequential kernel.  Otherwise the tokens per segment G of the chunk-parallel instantiation chosen: NW = 14 waves per
+ * (sequence, 64 channels) each own a run of steps of a segment, two passes joined by the linearity of the recurrence.  Launches of
+ * 56 < seqlen <= 196 tokens are one segment of 196 (14 steps per wave); 196 < seqlen <= 1024 walk ceil(seqlen / 140) segments of 140
+ * (10 steps per wave) and carry the fp32 state from one to the next.  The launch meant is one without last_state and without
+ * checkpoints, with arguments the family accepts (d_state 16, fp32 or I/O-dtype B/C, no DM_FLAG_OUT_ACCUMULATE); flags may carry
+ * DM_FLAG_SCAN_SEQUENTIAL / DM_FLAG_SCAN_CHUNKED.  Unforced, the library takes the family up to 512 channel-waves (nseq *
+ * ceil(dim / 64)); a launch past 196 tokens that writes checkpoints only up to 256.  Two congruent structs given to
+ * dm_selective_scan_fwd_n share one launch exactly where the family takes them. */
+int dm_scan_fwd_launch_segment(int nseq, int dim, int seqlen, int dstate, int flags);
 
 /* ------------------------------------------------------------------------------------------------
  * Selective scan, backward.  Replaces selective_scan_cuda.bwd (autograd of the above; training path
