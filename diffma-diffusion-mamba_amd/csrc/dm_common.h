@@ -356,4 +356,19 @@ __device__ __forceinline__ float slice_sum(float x) {
     return x;
 }
 
+// ---- host: dynamic LDS above the default limit ------------------------------------------------------------------------------
+// The limit is a per-DEVICE attribute of a kernel: raise it once per (device, kernel instantiation), not once per process (a
+// process that launches on a second GPU would otherwise fail there).  DM_OK, or DM_ERR_LAUNCH with the runtime's reason.
+template <auto KERNEL> static inline int reserve_dynamic_lds(const char* who, int bytes) {
+    static bool reserved[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("%s: cannot query the current device", who); return DM_ERR_LAUNCH; }
+    if (!reserved[dev]) {
+        const hipError_t r = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (r != hipSuccess) { set_error("%s: cannot reserve %d bytes of LDS: %s", who, bytes, hipGetErrorString(r)); return DM_ERR_LAUNCH; }
+        reserved[dev] = true;                         // benign race: two threads may both set the same value
+    }
+    return DM_OK;
+}
+
 }  // namespace dm

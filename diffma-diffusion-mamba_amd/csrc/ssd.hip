@@ -625,18 +625,9 @@ __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     }
 }
 
-// the dynamic-LDS limit of a kernel is a per-DEVICE attribute: set once per (device, instantiation), as dm_ssd_bwd does
 template <typename T, int NK>
 static int ssd_fwd_wide_launch(const dm_ssd_fwd_args& a, hipStream_t st) {
-    static bool reserved[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("dm_ssd_fwd: cannot query the current device"); return DM_ERR_LAUNCH; }
-    if (!reserved[dev]) {
-        constexpr int most = ssdw_lds_bytes(NK, SSD_MAXL);
-        const hipError_t r = hipFuncSetAttribute((const void*)ssd_fwd_wide_kernel<T, NK>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (r != hipSuccess) { set_error("dm_ssd_fwd: cannot reserve %d bytes of LDS: %s", most, hipGetErrorString(r)); return DM_ERR_LAUNCH; }
-        reserved[dev] = true;                         // benign race: two threads may both set the same value
-    }
+    if (const int rc = reserve_dynamic_lds<&ssd_fwd_wide_kernel<T, NK>>("dm_ssd_fwd", ssdw_lds_bytes(NK, SSD_MAXL))) return rc;
     const int rows = SSD_TILE * ((a.seqlen + SSD_TILE - 1) / SSD_TILE);
     dim3 grid((a.nheads + SSDW_HEADS - 1) / SSDW_HEADS, a.nseq), block(SSDW_THREADS);
     hipLaunchKernelGGL((ssd_fwd_wide_kernel<T, NK>), grid, block, ssdw_lds_bytes(NK, rows), st, a);

@@ -33,13 +33,10 @@ constexpr int SB_XS = 0;                          // X   [197][64]  16-byte chun
 constexpr int SB_GS = SB_XS + SB_ROWS * 128;      // gY  [197][64]  same layout
 constexpr int SB_BS = SB_GS + SB_ROWS * 128;      // B   [197][16]
 constexpr int SB_CS = SB_BS + SB_ROWS * 32;       // C   [197][16]
-constexpr int SB_TABS = SB_CS + SB_ROWS * 32;     // fp32 tables [T_NTAB][224]
-constexpr int SB_IDX = SB_TABS + T_NTAB * SB_TAB * 4;     // uint16 tables: z rows, dout rows
-constexpr int SB_STAGE = SB_IDX + 2 * SB_TAB * 2;         // 4 waves x [8][SB_STG] fp32
-constexpr int SB_RED = SB_STAGE + SB_WAVES * 8 * SB_STG * 4;   // block-reduction scratch
-constexpr int SB_LDS_BYTES = SB_RED + 128;
+constexpr int SB_TAIL = SB_CS + SB_ROWS * 32;     // tables, staging tiles, scratch (ssd_bwd_common.h)
+constexpr int SB_LDS_BYTES = SB_TAIL + SB_T_BYTES;
 static_assert(SB_LDS_BYTES <= 80 * 1024, "two workgroups per CU");
-static_assert(SB_TABS % 16 == 0 && SB_STAGE % 16 == 0, "16-byte aligned LDS arrays");
+static_assert(SB_TAIL % 16 == 0, "16-byte aligned LDS arrays");
 
 // 8 states of a B / C row
 __device__ __forceinline__ u32x4_t bc_frag(const uint8_t* base, int row, int kh) {
@@ -52,24 +49,12 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     using O = mfma<T>;
     constexpr int ES = (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    float* const tab = reinterpret_cast<float*>(lds + SB_TABS);
-    float* const DT = tab + T_DT * SB_TAB;
-    float* const CUM = tab + T_CUM * SB_TAB;
-    float* const S2 = tab + T_S2 * SB_TAB;
-    float* const ALPHA = tab + T_ALPHA * SB_TAB;
-    float* const GAM = tab + T_GAM * SB_TAB;
-    float* const GDT = tab + T_GDT * SB_TAB;
-    float* const SIG = tab + T_SIG * SB_TAB;
-    float* const RS = tab + T_RS * SB_TAB;
-    float* const CSV = tab + T_CS * SB_TAB;
-    uint16_t* const zi = reinterpret_cast<uint16_t*>(lds + SB_IDX);
-    uint16_t* const oi = zi + SB_TAB;
-    float* const red = reinterpret_cast<float*>(lds + SB_RED);
-
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const sb_tables t(lds + SB_TAIL, w);
+    const auto [DT, CUM, S2, ALPHA, GAM, GDT, SIG, RS, CSV, zi, oi, stage, red] = t;
     const int h = blockIdx.x, s = blockIdx.y;
-    const int L = p.seqlen, H = p.nheads;
+    const int L = p.seqlen;
     const int bpd = (p.batch_per_dir > 0) ? p.batch_per_dir : p.nseq;
     const int dir = s / bpd;
     const int sb = s - dir * bpd;
@@ -85,20 +70,12 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     const rsrc_t r_dx = make_rsrc((T*)p.dx + (int64_t)s * p.dx_ss);
     const rsrc_t r_dz = make_rsrc(p.dz ? (T*)p.dz + (int64_t)s * p.dz_ss : nullptr);
     const T* __restrict__ dtp = (const T*)p.dt + (int64_t)sb * p.dt_sb + h;
-    const int sl_x = (int)p.x_sl * ES, sl_B = (int)p.B_sl * ES, sl_C = (int)p.C_sl * ES, sl_z = (int)p.z_sl * ES;
+    const int sl_B = (int)p.B_sl * ES, sl_C = (int)p.C_sl * ES, sl_z = (int)p.z_sl * ES;
     const int sl_do = (int)p.do_sl * ES, sl_dx = (int)p.dx_sl * ES, sl_dz = (int)p.dz_sl * ES;
     const int hb = h * 64 * ES;                                                   // byte offset of the head's columns in a row
     float* const dbc_part = p.dBC_part + ((int64_t)h * p.nseq + s) * L * 32;          // head-major: the caller's sum over heads is a column sum
 
-    // ---- phases 0 + 1 (round 6): EVERY global load of the (sequence, head) is requested up front, in two dependent waves ----------
-    // Until round 6 the kernel walked a chain of ~6 memory latencies before its first MFMA (row indices -> dt -> [prefix sums] ->
-    // x / dout / z of chunk w -> the same of chunk w + 4 -> B / C half 0 -> half 1), each ended by LDS stores or a barrier, with only
-    // two workgroups per CU to cover for one another: 35 % of the wave-cycles parked at barriers, no unit busy
-    // (profiles/r05_m2_ssd_pmc.txt).  Now: level 1 = B / C, the x rows and the row-index entries (the thread's own position and the
-    // 4 rows the lane moves), level 2 = dt, dout, z through those indices -- 2 latencies; the tables are computed while level 2 flies.
-    // phase 1 role: wave w moves the 16-byte chunks w and w + 4 of every row; lane rows r = lane + 64 j
-    float dtv = 0.0f, sg0 = 0.0f;
-    int zr0 = 0, orow0 = 0;
+    // ---- phases 0 + 1: the load front (ssd_bwd_common.h), with B / C at its level 1 -----------------------------------------------
     u32x4_t bq[2], cq[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {                                                 // B / C: two 16-byte chunks per row, two rows per thread
@@ -110,38 +87,8 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
         bq[i] = (u32x4_t){b[0], b[1], b[2], b[3]};
         cq[i] = (u32x4_t){c[0], c[1], c[2], c[3]};
     }
-    const int pc = tid < L ? tid : L - 1;
-    if (zidx) { zr0 = zidx[pc]; orow0 = oidx[pc]; } else { zr0 = pc; orow0 = pc; }
-    int zrow[4], drow[4];
-    u32x4_t xq4[2][4], dq4[2][4], zq4[2][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int r = lane + 64 * j;
-        const int rc = r < L ? r : L - 1;
-        zrow[j] = zidx ? zidx[rc] : rc;
-        drow[j] = oidx ? oidx[rc] : rc;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const auto xq = __builtin_amdgcn_raw_buffer_load_b128(r_x, rc * sl_x + hb + (w + 4 * m) * 16, 0, 0);
-            xq4[m][j] = (u32x4_t){xq[0], xq[1], xq[2], xq[3]};
-        }
-    }
-    // level 2: through the indices
-    float rawv = 0.0f;
-    if (tid < L) rawv = io<T>::ld(dtp + (int64_t)zr0 * p.dt_sl);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int cb = hb + (w + 4 * m) * 16;
-            const auto dq = __builtin_amdgcn_raw_buffer_load_b128(r_do, drow[j] * sl_do + cb, 0, 0);
-            dq4[m][j] = (u32x4_t){dq[0], dq[1], dq[2], dq[3]};
-            zq4[m][j] = (u32x4_t){0u, 0u, 0u, 0u};
-            if (p.z) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zrow[j] * sl_z + cb, 0, 0);
-                zq4[m][j] = (u32x4_t){v[0], v[1], v[2], v[3]};
-            }
-        }
+    sb_front f;
+    sb_front_issue(f, p, r_x, r_do, zidx, oidx, dtp, hb, tid, lane, w, [&](int byte_off) -> u32x4_t { return ld16(r_z, byte_off); });
     // B / C into LDS (level 1 has landed by the time the dt value is needed)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -153,9 +100,11 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             *reinterpret_cast<u32x4_t*>(lds + SB_CS + r * 32 + hf * 16) = r < L ? cq[i] : zero4;
         }
     }
-    // per-position scalars (thread t <-> position t)
+    // per-position scalars (thread t <-> position t); kernel text in both kernels: as a shared function it costs K6b a fourth spill
+    float dtv = 0.0f, sg0 = 0.0f;
+    int zr0 = f.zr0, orow0 = f.orow0;
     if (tid < L) {
-        const float raw = rawv + bias;
+        const float raw = f.rawv + bias;
         dtv = softplus_f(raw);
         sg0 = (raw > 20.0f) ? 1.0f : sigmoid_f(raw);                               // d softplus / d raw (identity above 20)
     } else {
@@ -177,17 +126,16 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     }
     __syncthreads();
     if (tid < SB_TAB) {
-        const int t = tid >> 5;
+        const int tt = tid >> 5;
         const float sv = S2[tid];
-        const float m_t = t ? S2[SB_TILE * t - 1] : 0.0f, m_n = S2[SB_TILE * t + SB_TILE - 1];
+        const float m_t = tt ? S2[SB_TILE * tt - 1] : 0.0f, m_n = S2[SB_TILE * tt + SB_TILE - 1];
         const float al = fast_exp2(sv - m_t), ga = fast_exp2(m_n - sv);
         ALPHA[tid] = al;
         GAM[tid] = ga;
         GDT[tid] = ga * DT[tid];
     }
-    auto m_of = [&](int t) -> float { return t ? S2[SB_TILE * t - 1] : 0.0f; };   // log-decay just before tile t
 
-    // X, gY = dout .* silu(z) into LDS
+    // X, gY = dout .* silu(z) into LDS (kernel text, not a shared function: see ssd_bwd_common.h)
     float dD_acc = 0.0f;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -198,7 +146,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             if (r < SB_ROWS) {
                 u32x4_t xv = {0u, 0u, 0u, 0u}, gv = {0u, 0u, 0u, 0u};
                 if (r < L) {
-                    const u32x4_t xq = xq4[m][j], dq = dq4[m][j], zq = zq4[m][j];
+                    const u32x4_t xq = f.xq4[m][j], dq = f.dq4[m][j], zq = f.zq4[m][j];
 #pragma unroll
                     for (int d = 0; d < 4; ++d) {
                         float g0 = O::lo(dq[d]), g1 = O::hi(dq[d]);
@@ -222,7 +170,6 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     // ---- phase 2: the two orientations of the 28 tile pairs ---------------------------------------------------------------------
     const int q = lane & 31, kh = lane >> 5;                                      // fragment role: row/column of a tile, K half
     const int row8 = lane >> 3, c8 = lane & 7;                                    // epilogue role: row of an 8-row slab, 16-byte chunk
-    float* const stage = reinterpret_cast<float*>(lds + SB_STAGE) + w * 8 * SB_STG;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // selectors: a [positions x 64 channels] row-major fragment set times these = the 32-channel half nt in accumulator layout
     // (K-step j of the half: channel 32 nt + q sits in slot q - 16 j - 8 kh); states likewise (16 of them, columns 16-31 empty)
@@ -243,7 +190,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             u32x4_t gB[4];
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) gB[ks] = row_frag(lds + SB_GS, ql, 2 * ks + kh);
-            const float s2q = S2[ql], aq = ALPHA[ql], mlt = m_of(lt);
+            const float s2q = S2[ql], aq = ALPHA[ql], mlt = t.m_of(lt);
             u32x4_t zq4[4], dq4[4];                                             // the epilogue's z / dout pieces, in flight under the products
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
@@ -392,7 +339,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 const int qb = SB_TILE * lt + 4 * kh;
                 float mf[16];                                                     // M[query][key] (without dt)
                 if (lt > it) {
-                    const float ck = gamk * fast_exp2(m_of(lt) - mnext);
+                    const float ck = gamk * fast_exp2(t.m_of(lt) - mnext);
 #pragma unroll
                     for (int r4 = 0; r4 < 4; ++r4) {
                         const f32x4 a = *reinterpret_cast<const f32x4*>(&ALPHA[qb + 8 * r4]);
@@ -464,32 +411,15 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     }
     __syncthreads();
 
-    // ---- phase 3: d dt, dA, dD (thread t works on position 223 - t: the cumulative sum of d s runs from the end) ----------------
-    const int pos = SB_TAB - 1 - tid;
-    const bool live = tid < SB_TAB && pos < L;
-    float csv = 0.0f, dsv = 0.0f;
-    if (live) {
-        csv = CSV[pos];
-        dsv = RS[pos] - DT[pos] * csv;                                            // d s_l
-    }
-    const float rc = block_prefix_sum(dsv, lane, w, red + 24);                    // sum_{l >= pos} d s_l
-    const float draw = live ? (csv + Ah * rc) * SIG[pos] : 0.0f;                  // d(raw dt) through softplus
-    {
-        const float a = wave_sum_dpp(live ? dsv * CUM[pos] : 0.0f), d = wave_sum_dpp(dD_acc), b = wave_sum_dpp(draw);
-        if (lane == 0) {
-            red[w] = a;
-            red[8 + w] = d;
-            red[16 + w] = b;
-        }
-    }
-    if (live) p.ddt[((int64_t)s * L + zi[pos]) * H + h] = draw;
-    __syncthreads();
-    if (tid < 3) {                                                                // dA | dD | d dt_bias partial sums of this (sequence, head)
-        float t = 0.0f;
-#pragma unroll
-        for (int k = 0; k < SB_WAVES; ++k) t += red[8 * tid + k];
-        p.dAD_part[((int64_t)s * 3 + tid) * H + h] = t;
-    }
+    sb_phase3(p, t, s, h, tid, lane, w, Ah, dD_acc);
+}
+
+template <typename T>
+static int ssd_bwd_launch(const dm_ssd_bwd_args& a, hipStream_t st) {
+    if (const int rc = reserve_dynamic_lds<&ssd_bwd_kernel<T>>("dm_ssd_bwd", SB_LDS_BYTES)) return rc;
+    dim3 grid(a.nheads, a.nseq), block(SB_THREADS);
+    hipLaunchKernelGGL((ssd_bwd_kernel<T>), grid, block, SB_LDS_BYTES, st, a);
+    return launch_status("dm_ssd_bwd");
 }
 
 }  // namespace dm
@@ -500,40 +430,7 @@ extern "C" int dm_ssd_bwd_supported(int seqlen, int headdim, int dstate, int io_
 
 extern "C" int dm_ssd_bwd(const dm_ssd_bwd_args* args, void* stream) {
     using namespace dm;
-    if (!args) { set_error("dm_ssd_bwd: null args"); return DM_ERR_ARG; }
-    const dm_ssd_bwd_args& a = *args;
-    if (!a.x || !a.B || !a.C || !a.dt || !a.dout || !a.A || !a.dx || !a.dBC_part || !a.ddt || !a.dAD_part) {
-        set_error("dm_ssd_bwd: null tensor pointer"); return DM_ERR_ARG;
-    }
-    if ((a.z == nullptr) != (a.dz == nullptr)) { set_error("dm_ssd_bwd: z and dz go together"); return DM_ERR_ARG; }
-    if (a.nseq <= 0 || a.nheads <= 0 || a.seqlen <= 0) { set_error("dm_ssd_bwd: non-positive size"); return DM_ERR_ARG; }
-    if (!dm_ssd_bwd_supported(a.seqlen, a.headdim, a.dstate, a.io_dtype)) {
-        set_error("dm_ssd_bwd: needs 16-bit I/O, headdim 64, d_state 16, seqlen <= %d (got L %d P %d N %d dtype %d)", SB_MAXL, a.seqlen, a.headdim, a.dstate, a.io_dtype);
-        return DM_ERR_ARG;
-    }
-    if (a.nseq > 65535) { set_error("dm_ssd_bwd: nseq %d > 65535", a.nseq); return DM_ERR_ARG; }
-    if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) { set_error("dm_ssd_bwd: nseq %% batch_per_dir != 0"); return DM_ERR_ARG; }
-    if ((a.z_row_index == nullptr) != (a.out_row_index == nullptr)) { set_error("dm_ssd_bwd: both row-index tables or neither"); return DM_ERR_ARG; }
-    auto bad = [](const void* ptr, int64_t s0, int64_t s1) { return ((uintptr_t)ptr & 15) || (s0 & 7) || (s1 & 7); };
-    if (bad(a.x, a.x_ss, a.x_sl) || bad(a.B, a.B_ss, a.B_sl) || bad(a.C, a.C_ss, a.C_sl) || bad(a.dout, a.do_ss, a.do_sl) ||
-        bad(a.dx, a.dx_ss, a.dx_sl) || (a.z && (bad(a.z, a.z_ss, a.z_sl) || bad(a.dz, a.dz_ss, a.dz_sl)))) {
-        set_error("dm_ssd_bwd: rows must be 16-byte aligned (tiles move as 16-byte pieces)"); return DM_ERR_LAYOUT;
-    }
+    if (const int rc = ssd_bwd_check("dm_ssd_bwd", args, dm_ssd_bwd_supported, /*wide*/ false)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(a.nheads, a.nseq), block(SB_THREADS);
-    // the dynamic-LDS limit of a kernel is a per-DEVICE attribute: set it once per (device, instantiation), not once per process
-    // (a process that launches on a second GPU would otherwise fail there with 79 KB of dynamic LDS -- ADVICE r2)
-    static bool reserved[2][64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("dm_ssd_bwd: cannot query the current device"); return DM_ERR_LAUNCH; }
-    const int which = a.io_dtype == DM_BF16 ? 0 : 1;
-    if (!reserved[which][dev]) {
-        const hipError_t r = which == 0 ? hipFuncSetAttribute((const void*)ssd_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, SB_LDS_BYTES)
-                                        : hipFuncSetAttribute((const void*)ssd_bwd_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, SB_LDS_BYTES);
-        if (r != hipSuccess) { set_error("dm_ssd_bwd: cannot reserve %d bytes of LDS: %s", SB_LDS_BYTES, hipGetErrorString(r)); return DM_ERR_LAUNCH; }
-        reserved[which][dev] = true;                  // benign race: two threads may both set the same value
-    }
-    if (which == 0) hipLaunchKernelGGL((ssd_bwd_kernel<bf16_t>), grid, block, SB_LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((ssd_bwd_kernel<f16_t>), grid, block, SB_LDS_BYTES, st, a);
-    return launch_status("dm_ssd_bwd");
+    return args->io_dtype == DM_BF16 ? ssd_bwd_launch<bf16_t>(*args, st) : ssd_bwd_launch<f16_t>(*args, st);
 }

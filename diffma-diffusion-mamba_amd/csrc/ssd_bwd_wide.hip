@@ -27,13 +27,10 @@ constexpr int SBW_HEADS = DM_SSD_BWD_WIDE_HEADS;
 // LDS map (byte offsets); rows [L, 196] of the operand arrays are zero
 constexpr int SBW_XS = 0;                          // X   [197][64]  16-byte chunks XOR-swizzled by (row & 7)
 constexpr int SBW_GS = SBW_XS + SB_ROWS * 128;     // gY  [197][64]  same layout
-constexpr int SBW_TABS = SBW_GS + SB_ROWS * 128;   // fp32 tables [T_NTAB][224]
-constexpr int SBW_IDX = SBW_TABS + T_NTAB * SB_TAB * 4;     // uint16 tables: z rows, dout rows
-constexpr int SBW_STAGE = SBW_IDX + 2 * SB_TAB * 2;         // 4 waves x [8][SB_STG] fp32
-constexpr int SBW_RED = SBW_STAGE + SB_WAVES * 8 * SB_STG * 4;   // block-reduction scratch
-constexpr int SBW_LDS_BYTES = SBW_RED + 128;
+constexpr int SBW_TAIL = SBW_GS + SB_ROWS * 128;   // tables, staging tiles, scratch (ssd_bwd_common.h)
+constexpr int SBW_LDS_BYTES = SBW_TAIL + SB_T_BYTES;
 static_assert(SBW_LDS_BYTES <= 160 * 1024, "LDS of a CU");
-static_assert(SBW_TABS % 16 == 0 && SBW_STAGE % 16 == 0, "16-byte aligned LDS arrays");
+static_assert(SBW_TAIL % 16 == 0, "16-byte aligned LDS arrays");
 
 // NK fragments (8 states each at 16 j + 8 kh) of a B / C row, straight from global memory.  A row past L is never read: the lane
 // asks for row L - 1 instead and zeroes what comes back.
@@ -60,22 +57,10 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     constexpr int ES = (int)sizeof(T);
     constexpr int N = 16 * NK, NC = NK / 2;                                       // states; 32-state accumulator tiles of dB / dC
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    float* const tab = reinterpret_cast<float*>(lds + SBW_TABS);
-    float* const DT = tab + T_DT * SB_TAB;
-    float* const CUM = tab + T_CUM * SB_TAB;
-    float* const S2 = tab + T_S2 * SB_TAB;
-    float* const ALPHA = tab + T_ALPHA * SB_TAB;
-    float* const GAM = tab + T_GAM * SB_TAB;
-    float* const GDT = tab + T_GDT * SB_TAB;
-    float* const SIG = tab + T_SIG * SB_TAB;
-    float* const RS = tab + T_RS * SB_TAB;
-    float* const CSV = tab + T_CS * SB_TAB;
-    uint16_t* const zi = reinterpret_cast<uint16_t*>(lds + SBW_IDX);
-    uint16_t* const oi = zi + SB_TAB;
-    float* const red = reinterpret_cast<float*>(lds + SBW_RED);
-
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const sb_tables t(lds + SBW_TAIL, w);
+    const auto [DT, CUM, S2, ALPHA, GAM, GDT, SIG, RS, CSV, zi, oi, stage, red] = t;
     const int s = blockIdx.y;
     const int L = p.seqlen, H = p.nheads;
     const int bpd = (p.batch_per_dir > 0) ? p.batch_per_dir : p.nseq;
@@ -91,7 +76,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
     const rsrc_t r_do = make_rsrc((const T*)p.dout + (int64_t)s * p.do_ss);
     const rsrc_t r_dx = make_rsrc((T*)p.dx + (int64_t)s * p.dx_ss);
     const rsrc_t r_dz = make_rsrc(p.dz ? (T*)p.dz + (int64_t)s * p.dz_ss : nullptr);
-    const int sl_x = (int)p.x_sl * ES, sl_B = (int)p.B_sl * ES, sl_C = (int)p.C_sl * ES, sl_z = (int)p.z_sl * ES;
+    const int sl_B = (int)p.B_sl * ES, sl_C = (int)p.C_sl * ES, sl_z = (int)p.z_sl * ES;
     const int sl_do = (int)p.do_sl * ES, sl_dx = (int)p.dx_sl * ES, sl_dz = (int)p.dz_sl * ES;
     // the gate is a view of the in_proj output: its rows start on 16-byte boundaries with the factory models' 16 or 24 heads, on
     // 4-byte boundaries with the two heads of a d_model 64 mixer (then the same 16 bytes are read as dwords)
@@ -112,7 +97,6 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
 
     const int q = lane & 31, kh = lane >> 5;                                      // fragment role: row/column of a tile, K half
     const int row8 = lane >> 3, c8 = lane & 7;                                    // epilogue role: row of an 8-row slab, 16-byte chunk
-    float* const stage = reinterpret_cast<float*>(lds + SBW_STAGE) + w * 8 * SB_STG;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // selectors: a [positions x 32 channels / states] row-major fragment pair times these = those 32 columns in accumulator layout
     // (K-step j of the pair: column q sits in slot q - 16 j - 8 kh)
@@ -127,43 +111,16 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
         const T* __restrict__ dtp = (const T*)p.dt + (int64_t)sb * p.dt_sb + h;
         const int hb = h * 64 * ES;                                               // byte offset of the head's columns in a row
 
-        // ---- phases 0 + 1: every global load of the (sequence, head) is requested up front, in two dependent waves (ssd_bwd.hip) ----
-        // wave w moves the 16-byte chunks w and w + 4 of every row; lane rows r = lane + 64 j
+        // ---- phases 0 + 1: the load front (ssd_bwd_common.h) ----
+        sb_front f;
+        sb_front_issue(f, p, r_x, r_do, zidx, oidx, dtp, hb, tid, lane, w, z_piece);
+        // per-position scalars (thread t <-> position t); kernel text in both kernels: as a shared function it costs K6b a fourth spill
         float dtv = 0.0f, sg0 = 0.0f;
-        int zr0 = 0, orow0 = 0;
-        const int pc = tid < L ? tid : L - 1;
-        if (zidx) { zr0 = zidx[pc]; orow0 = oidx[pc]; } else { zr0 = pc; orow0 = pc; }
-        int zrow[4], drow[4];
-        u32x4_t xq4[2][4], dq4[2][4], zq4[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = lane + 64 * j;
-            const int rc = r < L ? r : L - 1;
-            zrow[j] = zidx ? zidx[rc] : rc;
-            drow[j] = oidx ? oidx[rc] : rc;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const auto xq = __builtin_amdgcn_raw_buffer_load_b128(r_x, rc * sl_x + hb + (w + 4 * m) * 16, 0, 0);
-                xq4[m][j] = (u32x4_t){xq[0], xq[1], xq[2], xq[3]};
-            }
-        }
-        float rawv = 0.0f;
-        if (tid < L) rawv = io<T>::ld(dtp + (int64_t)zr0 * p.dt_sl);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int cb = hb + (w + 4 * m) * 16;
-                const auto dq = __builtin_amdgcn_raw_buffer_load_b128(r_do, drow[j] * sl_do + cb, 0, 0);
-                dq4[m][j] = (u32x4_t){dq[0], dq[1], dq[2], dq[3]};
-                zq4[m][j] = (u32x4_t){0u, 0u, 0u, 0u};
-                if (p.z) zq4[m][j] = z_piece(zrow[j] * sl_z + cb);
-            }
-        // per-position scalars (thread t <-> position t)
+        int zr0 = f.zr0, orow0 = f.orow0;
         if (tid < L) {
-            const float raw = rawv + bias;
+            const float raw = f.rawv + bias;
             dtv = softplus_f(raw);
-            sg0 = (raw > 20.0f) ? 1.0f : sigmoid_f(raw);                           // d softplus / d raw (identity above 20)
+            sg0 = (raw > 20.0f) ? 1.0f : sigmoid_f(raw);                               // d softplus / d raw (identity above 20)
         } else {
             zr0 = 0;
             orow0 = 0;
@@ -175,25 +132,24 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
             oi[tid] = (uint16_t)orow0;
         }
         {
-            const float c = block_prefix_sum(dtv, lane, w, red);                   // cumsum(dt)
+            const float c = block_prefix_sum(dtv, lane, w, red);                       // cumsum(dt)
             if (tid < SB_TAB) {
                 CUM[tid] = c;
-                S2[tid] = a2 * c;                                                 // log2-domain log-decay
+                S2[tid] = a2 * c;                                                     // log2-domain log-decay
             }
         }
         __syncthreads();
         if (tid < SB_TAB) {
-            const int t = tid >> 5;
+            const int tt = tid >> 5;
             const float sv = S2[tid];
-            const float m_t = t ? S2[SB_TILE * t - 1] : 0.0f, m_n = S2[SB_TILE * t + SB_TILE - 1];
+            const float m_t = tt ? S2[SB_TILE * tt - 1] : 0.0f, m_n = S2[SB_TILE * tt + SB_TILE - 1];
             const float al = fast_exp2(sv - m_t), ga = fast_exp2(m_n - sv);
             ALPHA[tid] = al;
             GAM[tid] = ga;
             GDT[tid] = ga * DT[tid];
         }
-        auto m_of = [&](int t) -> float { return t ? S2[SB_TILE * t - 1] : 0.0f; };   // log-decay just before tile t
 
-        // X, gY = dout .* silu(z) into LDS
+        // X, gY = dout .* silu(z) into LDS (kernel text, not a shared function: see ssd_bwd_common.h)
         float dD_acc = 0.0f;
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
@@ -204,7 +160,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                 if (r < SB_ROWS) {
                     u32x4_t xv = {0u, 0u, 0u, 0u}, gv = {0u, 0u, 0u, 0u};
                     if (r < L) {
-                        const u32x4_t xq = xq4[m][j], dq = dq4[m][j], zq = zq4[m][j];
+                        const u32x4_t xq = f.xq4[m][j], dq = f.dq4[m][j], zq = f.zq4[m][j];
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
                             float g0 = O::lo(dq[d]), g1 = O::hi(dq[d]);
@@ -243,7 +199,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                 u32x4_t gB[4];
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) gB[ks] = row_frag(lds + SBW_GS, ql, 2 * ks + kh);
-                const float s2q = S2[ql], aq = ALPHA[ql], mlt = m_of(lt);
+                const float s2q = S2[ql], aq = ALPHA[ql], mlt = t.m_of(lt);
                 f32x16 Y0 = zero16, Y1 = zero16, dC[NC];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) dC[c] = zero16;
@@ -409,7 +365,7 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
                     const int qb = SB_TILE * lt + 4 * kh;
                     float mf[16];                                                 // M[query][key] (without dt)
                     if (lt > it) {
-                        const float ck = gamk * fast_exp2(m_of(lt) - mnext);
+                        const float ck = gamk * fast_exp2(t.m_of(lt) - mnext);
 #pragma unroll
                         for (int r4 = 0; r4 < 4; ++r4) {
                             const f32x4 a = *reinterpret_cast<const f32x4*>(&ALPHA[qb + 8 * r4]);
@@ -492,47 +448,14 @@ __global__ __launch_bounds__(SB_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1
         }
         __syncthreads();
 
-        // ---- phase 3: d dt, dA, dD (thread t works on position 223 - t: the cumulative sum of d s runs from the end) ------------
-        const int pos = SB_TAB - 1 - tid;
-        const bool live = tid < SB_TAB && pos < L;
-        float csv = 0.0f, dsv = 0.0f;
-        if (live) {
-            csv = CSV[pos];
-            dsv = RS[pos] - DT[pos] * csv;                                        // d s_l
-        }
-        const float rc = block_prefix_sum(dsv, lane, w, red + 24);                // sum_{l >= pos} d s_l
-        const float draw = live ? (csv + Ah * rc) * SIG[pos] : 0.0f;              // d(raw dt) through softplus
-        {
-            const float a = wave_sum_dpp(live ? dsv * CUM[pos] : 0.0f), d = wave_sum_dpp(dD_acc), b = wave_sum_dpp(draw);
-            if (lane == 0) {
-                red[w] = a;
-                red[8 + w] = d;
-                red[16 + w] = b;
-            }
-        }
-        if (live) p.ddt[((int64_t)s * L + zi[pos]) * H + h] = draw;
-        __syncthreads();
-        if (tid < 3) {                                                            // dA | dD | d dt_bias partial sums of this (sequence, head)
-            float t = 0.0f;
-#pragma unroll
-            for (int k = 0; k < SB_WAVES; ++k) t += red[8 * tid + k];
-            p.dAD_part[((int64_t)s * 3 + tid) * H + h] = t;
-        }
+        sb_phase3(p, t, s, h, tid, lane, w, Ah, dD_acc);
         __syncthreads();                                                          // the next head reuses the tables and the scratch
     }
 }
 
-// the dynamic-LDS limit of a kernel is a per-DEVICE attribute: set once per (device, instantiation), as ssd_fwd_wide_launch does
 template <typename T, int NK>
 static int ssd_bwd_wide_launch(const dm_ssd_bwd_args& a, hipStream_t st) {
-    static bool reserved[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("dm_ssd_bwd_wide: cannot query the current device"); return DM_ERR_LAUNCH; }
-    if (!reserved[dev]) {
-        const hipError_t r = hipFuncSetAttribute((const void*)ssd_bwd_wide_kernel<T, NK>, hipFuncAttributeMaxDynamicSharedMemorySize, SBW_LDS_BYTES);
-        if (r != hipSuccess) { set_error("dm_ssd_bwd_wide: cannot reserve %d bytes of LDS: %s", SBW_LDS_BYTES, hipGetErrorString(r)); return DM_ERR_LAUNCH; }
-        reserved[dev] = true;                         // benign race: two threads may both set the same value
-    }
+    if (const int rc = reserve_dynamic_lds<&ssd_bwd_wide_kernel<T, NK>>("dm_ssd_bwd_wide", SBW_LDS_BYTES)) return rc;
     dim3 grid((a.nheads + SBW_HEADS - 1) / SBW_HEADS, a.nseq), block(SB_THREADS);
     hipLaunchKernelGGL((ssd_bwd_wide_kernel<T, NK>), grid, block, SBW_LDS_BYTES, st, a);
     return launch_status("dm_ssd_bwd_wide");
@@ -556,26 +479,7 @@ extern "C" int dm_ssd_bwd_wide_supported(int seqlen, int headdim, int dstate, in
 
 extern "C" int dm_ssd_bwd_wide(const dm_ssd_bwd_args* args, void* stream) {
     using namespace dm;
-    if (!args) { set_error("dm_ssd_bwd_wide: null args"); return DM_ERR_ARG; }
-    const dm_ssd_bwd_args& a = *args;
-    if (!a.x || !a.B || !a.C || !a.dt || !a.dout || !a.A || !a.dx || !a.dBC_part || !a.ddt || !a.dAD_part) {
-        set_error("dm_ssd_bwd_wide: null tensor pointer"); return DM_ERR_ARG;
-    }
-    if ((a.z == nullptr) != (a.dz == nullptr)) { set_error("dm_ssd_bwd_wide: z and dz go together"); return DM_ERR_ARG; }
-    if (a.nseq <= 0 || a.nheads <= 0 || a.seqlen <= 0) { set_error("dm_ssd_bwd_wide: non-positive size"); return DM_ERR_ARG; }
-    if (!dm_ssd_bwd_wide_supported(a.seqlen, a.headdim, a.dstate, a.io_dtype)) {
-        set_error("dm_ssd_bwd_wide: needs 16-bit I/O, headdim 64, d_state 32 / 64 / 128, seqlen <= %d (got L %d P %d N %d dtype %d)", SB_MAXL, a.seqlen, a.headdim, a.dstate, a.io_dtype);
-        return DM_ERR_ARG;
-    }
-    if (a.nseq > 65535) { set_error("dm_ssd_bwd_wide: nseq %d > 65535", a.nseq); return DM_ERR_ARG; }
-    if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) { set_error("dm_ssd_bwd_wide: nseq %% batch_per_dir != 0"); return DM_ERR_ARG; }
-    if ((a.z_row_index == nullptr) != (a.out_row_index == nullptr)) { set_error("dm_ssd_bwd_wide: both row-index tables or neither"); return DM_ERR_ARG; }
-    auto bad = [](const void* ptr, int64_t s0, int64_t s1) { return ((uintptr_t)ptr & 15) || (s0 & 7) || (s1 & 7); };
-    if (bad(a.x, a.x_ss, a.x_sl) || bad(a.B, a.B_ss, a.B_sl) || bad(a.C, a.C_ss, a.C_sl) || bad(a.dout, a.do_ss, a.do_sl) ||
-        bad(a.dx, a.dx_ss, a.dx_sl) || (a.dz && bad(a.dz, a.dz_ss, a.dz_sl))) {
-        set_error("dm_ssd_bwd_wide: x / B / C / dout / dx / dz rows must be 16-byte aligned (tiles move as 16-byte pieces)"); return DM_ERR_LAYOUT;
-    }
-    if (a.z && (((uintptr_t)a.z & 3) || (a.z_ss & 1) || (a.z_sl & 1))) { set_error("dm_ssd_bwd_wide: z rows must be 4-byte aligned"); return DM_ERR_LAYOUT; }
+    if (const int rc = ssd_bwd_check("dm_ssd_bwd_wide", args, dm_ssd_bwd_wide_supported, /*wide*/ true)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return a.io_dtype == DM_BF16 ? ssd_bwd_wide_dispatch<bf16_t>(a, st) : ssd_bwd_wide_dispatch<f16_t>(a, st);
+    return args->io_dtype == DM_BF16 ? ssd_bwd_wide_dispatch<bf16_t>(*args, st) : ssd_bwd_wide_dispatch<f16_t>(*args, st);
 }

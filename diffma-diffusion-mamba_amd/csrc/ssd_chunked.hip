@@ -440,18 +440,10 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
     }
 }
 
-// the dynamic-LDS limit of a kernel is a per-DEVICE attribute: set once per (device, instantiation), as dm_ssd_fwd does
 template <typename T, int NK>
 static int ssd_fwd_chunked_launch(const dm_ssd_fwd_args& a, hipStream_t st) {
-    constexpr int Q = ssdc_q(NK), most = ssdc_lds_bytes(NK, Q);
-    static bool reserved[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("dm_ssd_fwd_chunked: cannot query the current device"); return DM_ERR_LAUNCH; }
-    if (!reserved[dev]) {
-        const hipError_t r = hipFuncSetAttribute((const void*)ssd_fwd_chunked_kernel<T, NK>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (r != hipSuccess) { set_error("dm_ssd_fwd_chunked: cannot reserve %d bytes of LDS: %s", most, hipGetErrorString(r)); return DM_ERR_LAUNCH; }
-        reserved[dev] = true;                         // benign race: two threads may both set the same value
-    }
+    constexpr int Q = ssdc_q(NK);
+    if (const int rc = reserve_dynamic_lds<&ssd_fwd_chunked_kernel<T, NK>>("dm_ssd_fwd_chunked", ssdc_lds_bytes(NK, Q))) return rc;
     const int rows = a.seqlen < Q ? SSDC_TILE * ((a.seqlen + SSDC_TILE - 1) / SSDC_TILE) : Q;
     dim3 grid((a.nheads + SSDC_HEADS - 1) / SSDC_HEADS, a.nseq), block(2 * WAVE * SSDC_HEADS);
     hipLaunchKernelGGL((ssd_fwd_chunked_kernel<T, NK>), grid, block, ssdc_lds_bytes(NK, rows), st, a);

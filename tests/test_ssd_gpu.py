@@ -53,9 +53,9 @@ tile rounding adds u |g delta| + T, so per pair
 The last line is the epilogue (:272-274): + D x and the gate in fp32 (silu_f: one v_exp_f32, one v_rcp_f32), one rounding of the result.
 First order: 3 u S_l + u |ref_l| with S_l = (Wabs |X|)_l.
 
-Backward (ssd_bwd.hip).  16-bit roundings: gY = rnd(dout silu(z)) (:264; dD uses the unrounded value, :262); the W tile rnd(G Mdt)
-(:356 T orientation, :468 N); the dG tile rnd(R Mdt) (:357, :469); the outputs dz (:408) and dx (:511).  The one-hot products
-(:329-331, :442-444) multiply by 1.0 and are exact; G and R are fp32 sums of exact products; the row / column sums of V (:355, :467) take
+Backward (ssd_bwd.hip).  16-bit roundings: gY = rnd(dout silu(z)) (:159; dD uses the unrounded value, :157); the W tile rnd(G Mdt)
+(:250 T orientation, :362 N); the dG tile rnd(R Mdt) (:251, :363); the outputs dz (:302) and dx (:405).  The one-hot products
+(:223-225, :336-338) multiply by 1.0 and are exact; G and R are fp32 sums of exact products; the row / column sums of V (:249, :361) take
 the fp32 values before the tile is rounded; dB / dC / d dt / dA / dD / d dt_bias leave in fp32.  With dg = u |gY| + T (error of the
 stored gY), dR = dg |X|^T:
     dz        1 + 1 roundings   |dout silu'(z)|_abs ((u + C32) Wabs + T) |X| (1 + u) + (u + c_z) |ref| + T      (silu' is computed as
