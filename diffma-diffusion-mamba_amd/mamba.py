@@ -18,8 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .selective_scan_interface import (gate_in_dgrad_wanted, linear_pair, linear_splitk, spiral_ssm, spiral_ssm_out_proj, spiral_ssm_pair,
-                                       spiral_ssm_pair_supported)
+from .projections import linear_pair, linear_splitk
+from .selective_scan_interface import gate_in_dgrad_wanted, spiral_ssm, spiral_ssm_out_proj, spiral_ssm_pair, spiral_ssm_pair_supported
 from .tools import efficient_scan_tokens
 
 

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .selective_scan_interface import linear_splitk, spiral_ssd
+from .projections import linear_splitk
+from .selective_scan_interface import spiral_ssd
 
 
 class RMSNorm(nn.Module):

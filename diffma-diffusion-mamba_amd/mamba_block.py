@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import block_ops, hip_ops
 from .mamba import Mamba, forward_pair
-from .selective_scan_interface import GemmChain, _mm_f32, linear_splitk
+from .projections import GemmChain, _mm_f32, linear_splitk
 
 
 _SILU_ONCE = [None]

@@ -19,7 +19,8 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import _lib, hip_ops
+from . import _lib, hip_ops, projections as proj
+from .projections import DGRAD, FWD, INNER_PAIR, INNER_SINGLE, SINGLE, WGRAD, GemmChain, linear_pair, linear_splitk, product     # noqa: F401 (GemmChain, linear_pair: public here)
 from .step_prep import cast_weight, stacked_pair
 
 
@@ -180,263 +181,16 @@ def causal_conv1d_fn(x, weight, bias=None, seq_idx=None, initial_states=None, re
     return _CausalConv1dFn.apply(x, weight, bias, activation is not None)
 
 
-class GemmChain:
-    """Used only by the opt-in two-stream mode of the block (mamba_block.Spiral_MambaBlock._mixers): every GEMM of the two
-    mixer streams is chained behind the previous one with an event, so that no two library GEMMs are ever resident together.
-    hipBLASLt / Tensile's persistent stream-K kernels spin-wait for their own not-yet-scheduled workgroups; two of them
-    co-scheduled from two queues can starve each other (observed as a GPU hang).  GEMM next to scan / conv / merge kernels
-    stays concurrent -- those workgroups always retire."""
-    enabled = False
-    event = None
-    stream = None
-
-    @classmethod
-    def run(cls, fn, *args, **kw):
-        if not cls.enabled or not torch.cuda.is_available():
-            return fn(*args, **kw)
-        cur = torch.cuda.current_stream()
-        if cls.event is not None and cls.stream != cur:
-            cur.wait_event(cls.event)
-        out = fn(*args, **kw)
-        cls.event = torch.cuda.Event()
-        cls.event.record(cur)
-        cls.stream = cur
-        return out
-
-
-def _tn_splitk(a, b):
-    return GemmChain.run(_tn_splitk_impl, a, b)
-
-
-_MM_F32 = [None]          # does torch.mm take out_dtype on this device?  (aten::mm.dtype: 16-bit operands, fp32 result, one launch)
-
-
-def _mm_f32(x, y):
-    """x @ y in fp32 from 16-bit operands WITHOUT a separate cast launch where the library offers it (hipBLASLt accumulates in fp32
-    anyway; the 16-bit result + `.float()` of the plain form rounds the weight gradient once more and costs a launch per GEMM -- ~150 per
-    training step, which is what a small-batch step is made of)."""
-    if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and _MM_F32[0] is not False:
-        try:
-            out = torch.mm(x, y, out_dtype=torch.float32)
-            _MM_F32[0] = True
-            return out
-        except (RuntimeError, NotImplementedError, TypeError):
-            if _MM_F32[0]:                       # it worked before: a real error, not a missing feature
-                raise
-            _MM_F32[0] = False
-    return (x @ y).float()
-
-
-def _tn_splitk_impl(a, b):
-    """a^T @ b for tall operands a (M, P), b (M, Q): the reduction runs over M = B*L or ndir*B*L (50 176 /
-    150 528 at the bench shape), which hipBLASLt does not split -- a single-pass GEMM is 2-8x off its memory
-    time (x_proj: 492 us vs 82 us; in_proj: 194 us vs 128 us even after solution tuning; tools/bench_gemm.py).
-    Split K into C slabs with one bmm and add the slabs in fp32; C is bounded so that the slab outputs stay
-    small next to the operands."""
-    M = a.shape[0]
-
-    def slabs(t, C):
-        """[M, P] (row stride >= P: a column block of a wider row-major buffer is fine, bmm takes the leading dimension) -> [C, M/C, P]"""
-        return t.as_strided((C, M // C, t.shape[1]), (M // C * t.stride(0), t.stride(0), 1))
-
-    for C in (64, 32, 16, 8):
-        # (below ~12k rows one GEMM is as fast as the slab product + its sum, and it is one launch instead of two: the small-batch step
-        #  is made of launches)
-        if M >= 12288 and M % C == 0 and M // C >= 256 and C * a.shape[1] * b.shape[1] <= (1 << 23) and a.stride(1) == 1 and b.stride(1) == 1:
-            return torch.bmm(slabs(a, C).transpose(1, 2), slabs(b, C)).sum(0, dtype=torch.float32)      # the cast is fused into the reduction
-    return _mm_f32(a.t(), b)
-
-
-def _own_single(a, b, a_kmajor, b_kmajor, out_dtype=None):
-    """dm_gemm for ONE product: same row bound as the paired form, and only for matrices with at least 64 rows (below that a GEMM
-    is a handful of workgroups either way)."""
-    rows = a.shape[0]
-    return (64 <= rows <= PAIR_OWN_MAX_ROWS and a.dim() == 2 and b.dim() == 2
-            and hip_ops.gemm_supported(a, b, a_kmajor, b_kmajor, out_dtype))
-
-
-# Large-batch projections on K12 (csrc/gemm_large.hip).  DIFFMA_GEMM_LARGE=0 (hip_ops.GEMM_LARGE) returns every product to the library.
-# DIFFMA_GEMM_LARGE_MIN_COLS: K12 is taken from this many output columns.  Measured against the TunableOp-tuned library at M = 100 352
-# (profiles/r05_gemm_large_ablation.txt, stand-alone): N = 2048 and 1024 level or ahead (in_proj forward 216 vs 222 us, out_proj
-# input gradient 108 vs 125 / 148 us), N = 512 level (out_proj forward 104 vs 105) or behind (in_proj input gradient, K = 2048: 223 vs
-# 198).  Inside the training step K12's launches run ~10 % longer than stand-alone and the step is 0.5 % SLOWER with K12 on the two
-# wide products than with the library everywhere (220.1 vs 219.1 ms, same box; 221.9 with K12 on all four): at parity, not ahead.
-# The default keeps it on the wide products; DIFFMA_GEMM_LARGE_MIN_COLS=512 puts all four on it.
-LARGE_MIN_ROWS = int(os.environ.get("DIFFMA_GEMM_LARGE_MIN_ROWS", "12288"))
-LARGE_MIN_COLS = int(os.environ.get("DIFFMA_GEMM_LARGE_MIN_COLS", "1024"))
-LARGE_MAX_K_NARROW = int(os.environ.get("DIFFMA_GEMM_LARGE_MAX_K_NARROW", "1024"))     # for outputs narrower than 1024 columns
-# dx = dy W as dy (W^T)^T with a transposed 16-bit weight copy: the library's NT kernels beat its NN kernels at these shapes
-LARGE_DGRAD_NT = os.environ.get("DIFFMA_DGRAD_NT", "1") == "1"
-
-
-def _own_large(a, b):
-    """dm_gemm_large for C = a @ b^T (a [M, K], b [N, K], both 16-bit, K contiguous)?"""
-    M, K = a.shape
-    N = b.shape[0]
-    if M < LARGE_MIN_ROWS or N < LARGE_MIN_COLS or (N < 1024 and K > LARGE_MAX_K_NARROW):
-        return False
-    return hip_ops.gemm_large_supported(a, b)
-
-
-class _LinearSplitKFn(torch.autograd.Function):
-    """F.linear whose weight gradient uses the split-K product above (the projections' dW GEMMs have K = B*L)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        dev = x.device.type
-        dt_ = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else x.dtype
-        xc = x if x.dtype == dt_ else x.to(dt_)
-        wc = cast_weight(weight, dt_)                    # the step's shadow copy when current (step_prep), else a cast
-        ctx.save_for_backward(xc, wc)
-        ctx.meta = (x.dtype, weight.dtype, None if bias is None else bias.dtype)
-        if bias is None and xc.is_cuda and _own_single(xc.reshape(-1, xc.shape[-1]), wc, True, True):
-            # small launches: the own kernel is faster than the library's quantised tile grid (csrc/gemm.hip)
-            return hip_ops.gemm(xc.reshape(-1, xc.shape[-1]), wc).view(*xc.shape[:-1], wc.shape[0])
-        if bias is None and xc.is_cuda and _own_large(xc.reshape(-1, xc.shape[-1]), wc):
-            # large batch: the persistent 256 x 256 kernel (csrc/gemm_large.hip, K12)
-            return hip_ops.gemm_large(xc.reshape(-1, xc.shape[-1]), wc).view(*xc.shape[:-1], wc.shape[0])
-        return GemmChain.run(F.linear, xc, wc, None if bias is None else cast_weight(bias, dt_))
-
-    @staticmethod
-    def backward(ctx, dy):
-        xc, wc = ctx.saved_tensors
-        x_dt, w_dt, b_dt = ctx.meta
-        with torch.autocast(device_type=xc.device.type, enabled=False):
-            dy2 = dy.reshape(-1, dy.shape[-1])
-            if dy2.dtype != xc.dtype:
-                dy2 = dy2.to(xc.dtype)
-            x2 = xc.reshape(-1, xc.shape[-1])
-            dy2c, x2c = dy2.contiguous(), x2.contiguous()
-            dx = _linear_dgrad(dy2, dy2c, wc, b_dt is None).view(xc.shape).to(x_dt) if ctx.needs_input_grad[0] else None
-            dw = _linear_wgrad(dy2c, x2c, b_dt is None).to(w_dt) if ctx.needs_input_grad[1] else None
-            db = dy2.sum(0, dtype=torch.float32).to(b_dt) if (b_dt is not None and ctx.needs_input_grad[2]) else None
-        return dx, dw, db
-
-
-def _large_dgrad_nt(dy2c):
-    """The input gradient as an "NT" product with a transposed 16-bit copy of the weight?"""
-    return LARGE_DGRAD_NT and dy2c.is_cuda and dy2c.shape[0] >= LARGE_MIN_ROWS and dy2c.dtype in (torch.bfloat16, torch.float16)
-
-
-def _linear_dgrad(dy2, dy2c, wc, no_bias):
-    """dx [M, K] = dy2 [M, N] @ wc [N, K] of a projection (dy2c: dy2 made contiguous)."""
-    if no_bias and _own_single(dy2c, wc, True, False):
-        return hip_ops.gemm(dy2c, wc, True, False)
-    if _large_dgrad_nt(dy2c):
-        # dx = dy W as an "NT" product with a transposed 16-bit copy of the weight (a few MB, one small launch): both
-        # operands then have the contraction index contiguous.  Measured at M = 100 352 (tools/bench_gemm_large.py): the
-        # library's NN form 217 / 148 us (in_proj / out_proj) against 198 / 125 us for its NT form and 223 / 108 us for K12.
-        wt = wc.t().contiguous()
-        if _own_large(dy2c, wt):
-            return hip_ops.gemm_large(dy2c, wt)
-        return GemmChain.run(F.linear, dy2c, wt)
-    return GemmChain.run(torch.mm, dy2, wc)
-
-
-def _linear_wgrad(dy2c, x2c, no_bias):
-    """dW [N, K] fp32 = dy2c^T @ x2c."""
-    if no_bias and _own_single(dy2c, x2c, False, False, torch.float32):
-        return hip_ops.gemm(dy2c, x2c, False, False, out_dtype=torch.float32)
-    return _tn_splitk(dy2c, x2c)
-
-
-def linear_splitk(x, weight, bias=None):
-    """Drop-in for F.linear(x, weight, bias) on the token-major projections (in_proj / out_proj)."""
-    return _LinearSplitKFn.apply(x, weight, bias)
-
-
 # ------------------------------------------------------------------------------------------------
 # The TWO mixers of a DiffMa block as one set of launches (reference block/mamba_block.py:107-108)
 # ------------------------------------------------------------------------------------------------
 # The reference runs mamba1(x_ssm) and mamba2(w_ssm) one after the other: same shapes, different weights and spiral tables.  Its own
 # configuration trains at ONE sample per GPU (config/brain.yaml:11), where a step is bound by the number of kernel launches (eager:
 # the host's launch rate; hipGraph: ~8 us of dispatch per node), not by what the kernels do.  The pair path issues every stage once
-# for both mixers: the projections as batched GEMMs over stacked weights, the kernels through hip_ops.both() -> the `_n` entry
+# for both mixers: the projections through projections.linear_pair / `product`, the kernels through hip_ops.both() -> the `_n` entry
 # points of the C ABI (one grid, blockIdx.z picks the mixer).  Arithmetic per mixer is unchanged: kernels bit-identical, GEMMs to
 # library rounding.  Used for small launches only (below the fused conv + x_proj threshold); large batches gain nothing from it.
 PAIR_MIXERS = os.environ.get("DIFFMA_PAIR_MIXERS", "1") == "1"
-
-# The pair path's projections run on dm_gemm (csrc/gemm.hip), ONE launch for both mixers through hip_ops.both(), up to PAIR_OWN_MAX_ROWS
-# rows per mixer, where it is also faster on the device than the library's two GEMMs (DiffMa-L/2 widths, both mixers, us incl. launch,
-# tools/bench_gemm_own.py: batch 8 in_proj 43 -> 21 forward, 42 -> 30 weight gradient, out_proj 41 -> 16 / 38 -> 15 / 40 -> 22; from
-# ~6 000 rows the library's large tiles win).  Above that, and for shapes dm_gemm does not take: one plain library GEMM per mixer --
-# the products the unpaired path has always issued, tuned and recorded (a batch-2 library GEMM is not safe here: DESIGN.md section 7).
-PAIR_OWN_MAX_ROWS = int(os.environ.get("DIFFMA_PAIR_OWN_MAX_ROWS", "3200"))
-
-
-def _pair_use_own(rows, a, b, a_kmajor, b_kmajor, out_dtype=None):
-    return rows <= PAIR_OWN_MAX_ROWS and hip_ops.gemm_supported(a, b, a_kmajor, b_kmajor, out_dtype)
-
-
-def _own_pair(a, b, a_kmajor, b_kmajor, out, accumulate=False):
-    """out[g] (+)= opA(a[g]) @ opB(b[g]) for g = 0, 1 in ONE launch (dm_gemm_n)."""
-    hip_ops.both(lambda g: hip_ops.gemm(a[g], b[g], a_kmajor, b_kmajor, out=out[g], accumulate=accumulate))
-    return out
-
-
-def _pair_matmul(x, y):
-    """x [2, P, Q] @ y [2, Q, R] -> [2, P, R]: one library GEMM per mixer."""
-    out = torch.empty((2, x.shape[1], y.shape[2]), dtype=x.dtype, device=x.device)
-    for g in (0, 1):
-        GemmChain.run(torch.mm, x[g], y[g], out=out[g])
-    return out
-
-
-def _as_pair(a, b):
-    """[2, ...] tensor holding a and b: the shared buffer when they already are its two halves (no copy), else a stack."""
-    if (a.shape == b.shape and a.dtype == b.dtype and a.is_contiguous() and b.is_contiguous()
-            and b.data_ptr() == a.data_ptr() + a.numel() * a.element_size() and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()):
-        return torch.as_strided(a, (2,) + tuple(a.shape), (a.numel(),) + tuple(a.stride()))
-    return torch.stack([a, b])
-
-
-class _LinearPairFn(torch.autograd.Function):
-    """(x0 @ W0^T, x1 @ W1^T) as ONE batched GEMM each way; bias-free (in_proj / out_proj of the mixers, block/mamba.py:259-261,315)."""
-
-    @staticmethod
-    def forward(ctx, x0, x1, W0, W1):
-        dev = x0.device.type
-        dt_ = torch.get_autocast_dtype(dev) if torch.is_autocast_enabled(dev) else x0.dtype
-        xp = _as_pair(x0 if x0.dtype == dt_ else x0.to(dt_), x1 if x1.dtype == dt_ else x1.to(dt_))       # [2, B, L, K]
-        Wst = stacked_pair(W0, W1, dt_)                                                                   # [2, N, K]
-        ctx.save_for_backward(xp, Wst)
-        ctx.meta = (x0.dtype, W0.dtype)
-        K = xp.shape[-1]
-        x2 = xp.view(2, -1, K)
-        if _pair_use_own(x2.shape[1], x2[0], Wst[0], True, True):
-            y = _own_pair(x2, Wst, True, True, torch.empty((2, x2.shape[1], Wst.shape[1]), dtype=dt_, device=xp.device))
-        else:
-            y = _pair_matmul(x2, Wst.transpose(1, 2))                                                      # [2, M, N]
-        y = y.view(2, *x0.shape[:-1], Wst.shape[1])
-        return y[0], y[1]
-
-    @staticmethod
-    def backward(ctx, dy0, dy1):
-        xp, Wst = ctx.saved_tensors
-        x_dt, w_dt = ctx.meta
-        with torch.autocast(device_type=xp.device.type, enabled=False):
-            N, K = Wst.shape[1], Wst.shape[2]
-            dy = _as_pair(dy0.contiguous() if dy0.dtype == xp.dtype else dy0.contiguous().to(xp.dtype),
-                          dy1.contiguous() if dy1.dtype == xp.dtype else dy1.contiguous().to(xp.dtype)).view(2, -1, N)
-            x2 = xp.view(2, -1, K)
-            M = dy.shape[1]
-            if _pair_use_own(M, dy[0], Wst[0], True, False):
-                dx = _own_pair(dy, Wst, True, False, torch.empty((2, M, K), dtype=dy.dtype, device=dy.device)).view(xp.shape)
-            else:
-                dx = _pair_matmul(dy, Wst).view(xp.shape)
-            if dx.dtype != x_dt:
-                dx = dx.to(x_dt)
-            if _pair_use_own(M, dy[0], x2[0], False, False, torch.float32):
-                dW = _own_pair(dy, x2, False, False, torch.empty((2, N, K), dtype=torch.float32, device=dy.device))
-            else:
-                dW = (_tn_splitk(dy[0], x2[0]), _tn_splitk(dy[1], x2[1]))                                  # the unpaired path's products
-            dW0, dW1 = (dW[0], dW[1]) if w_dt == torch.float32 else (dW[0].to(w_dt), dW[1].to(w_dt))
-        return dx[0], dx[1], dW0, dW1
-
-
-def linear_pair(x0, x1, W0, W1):
-    """(F.linear(x0, W0), F.linear(x1, W1)) for the two mixers of a block: one batched GEMM forward, two backward."""
-    return _LinearPairFn.apply(x0, x1, W0, W1)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -444,12 +198,6 @@ def linear_pair(x0, x1, W0, W1):
 # ------------------------------------------------------------------------------------------------
 # DIFFMA_HOIST_GATE=0: gate (and softplus) back inside every per-direction scan, as upstream evaluates them (A/B runs, tests)
 HOIST_GATE = os.environ.get("DIFFMA_HOIST_GATE", "1") == "1"
-
-
-def _inner_on_own(G, M, a, b, a_kmajor, b_kmajor, out_dtype=None):
-    """The operator's inner projections (x_proj forward, dWx, du += dx_dbl @ Wx) on dm_gemm: a choice of the pair alone; the single
-    mixer keeps them on the library.  (64-column products: the own kernel holds up to ~4x the rows.)"""
-    return G == 2 and _pair_use_own(M // 4, a, b, a_kmajor, b_kmajor, out_dtype)
 
 
 class _SpiralSSMFn(torch.autograd.Function):
@@ -481,7 +229,7 @@ class _SpiralSSMFn(torch.autograd.Function):
         gradient (_GatedOutProjFn).  Taken when the gate is hoisted and a backward will run: the outputs are then (y, pre), y not
         differentiable, and the gradient that arrives for `pre` IS g = dy * silu(z)."""
         xz, idx, cw, cb, Wx, Wdt, bias, A, Dk = (ops[i * G:(i + 1) * G] for i in range(_SpiralSSMFn.NFIELD))
-        stage, each = _SpiralSSMFn._stage(G), range(G)
+        stage, each, inner = _SpiralSSMFn._stage(G), range(G), (INNER_PAIR if G == 2 else INNER_SINGLE)
         Bsz, L, D2 = xz[0].shape
         Din = D2 // 2
         ndir = idx[0].shape[0]
@@ -501,12 +249,9 @@ class _SpiralSSMFn(torch.autograd.Function):
         else:
             xc = torch.empty((G, S, L, Din), dtype=dt_, device=dev)
             stage(lambda g: hip_ops.gather_conv1d_fwd(xz[g][..., :Din], cw[g], cb[g], row_index=idx[g], ndir=ndir, silu=True, out=xc[g]))
-            # x_proj is one product per mixer: as a batch-2 GEMM its [M, 1024] x [1024, 64] shape makes TunableOp's first-use tuning
-            # run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop)
-            if _inner_on_own(G, M, xc[0].view(M, Din), Wx_c[0], True, True):
-                x_dbl = _own_pair(xc.view(G, M, Din), Wx_c, True, True, torch.empty((G, M, R + 2 * N), dtype=dt_, device=dev))
-            else:
-                x_dbl = [GemmChain.run(F.linear, xc[g].view(M, Din), Wx_c[g]) for g in each]          # [ndir*B*L, R+2N]
+            # x_proj on the library is one product per mixer: as a batch-2 GEMM its [M, 1024] x [1024, 64] shape makes TunableOp's first-use
+            # tuning run a library candidate that faults (MI355X, ROCm 7.2: memory access fault inside the tuning loop)
+            x_dbl = product(FWD, inner, xc.view(G, M, Din), Wx_c)                                             # G x [ndir*B*L, R+2N]
         # Hoisted gate: CrossScan permutes x and z together and CrossMerge applies the inverse permutation (block/mamba.py:41-45,
         # 66-68), so merged[t] = silu(z[t]) * sum_k y~_k[t]: the scans run WITHOUT z and the gate is applied once per token by the
         # merge (one z read in an HBM-bound kernel) instead of three times inside the VALU-bound scans.  Needs the scatter table
@@ -522,7 +267,7 @@ class _SpiralSSMFn(torch.autograd.Function):
         if act:
             delta = stage(lambda g: hip_ops.dtproj_softplus_fwd(x_dbl[g], Wdt_c[g], bias[g]).view(S, L, Din))
         else:
-            delta = [GemmChain.run(F.linear, x_dbl[g][:, :R], Wdt_c[g]).view(S, L, Din) for g in each]
+            delta = [t.view(S, L, Din) for t in product(FWD, INNER_SINGLE, [t[:, :R] for t in x_dbl], Wdt_c)]
         ckpt = [hip_ops.alloc_scan_ckpt(S, L, N, Din, dt_, dev) if need_grad else None for _ in each]
         oidx = idx if out_index is None else (out_index,)
         xd3 = [t.view(S, L, R + 2 * N) for t in x_dbl]
@@ -559,7 +304,7 @@ class _SpiralSSMFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         xz, idx, oidx, cw, cb, bias, A, Dk, xc, x_dbl, delta, ckpt, pre = (sv[i * G:(i + 1) * G] for i in range(13))
         Wx_c, Wdt_c = sv[-2:]
-        stage, each = _SpiralSSMFn._stage(G), range(G)
+        stage, each, inner = _SpiralSSMFn._stage(G), range(G), (INNER_PAIR if G == 2 else INNER_SINGLE)
         Bsz, L, D2 = xz[0].shape
         Din = D2 // 2
         ndir = idx[0].shape[0]
@@ -596,15 +341,10 @@ class _SpiralSSMFn(torch.autograd.Function):
             # both consumers of ddelta -- the dt columns of d(x_dbl) and dW_dt -- in ONE read of it (csrc/dtproj.hip, K8b)
             dWdt = stage(lambda g: hip_ops.dtproj_bwd(ddelta[g], x_dbl[g], Wdt_c[g], dx_dbl[g]))
         else:
-            dWdt = []
-            for g in each:
-                dx_dbl[g][:, :R] = GemmChain.run(torch.mm, ddelta[g], Wdt_c[g])   # (a strided `out=` is an untuned GEMM shape class: pathologically slow by default)
-                dWdt.append(_tn_splitk(ddelta[g], x_dbl[g][:, :R]))               # [Din, R]; the dt columns of x_dbl in place (leading dimension R + 2N)
-        xc2 = [t.view(M, Din) for t in xc]
-        if _inner_on_own(G, M, dx_dbl[0], xc2[0], False, False, torch.float32):
-            dWx = _own_pair(dx_dbl, xc2, False, False, torch.empty((G, R + 2 * N, Din), dtype=torch.float32, device=dev))
-        else:
-            dWx = [_tn_splitk(dx_dbl[g], xc2[g]) for g in each]                   # [R+2N, Din] fp32 each
+            for g, t in enumerate(product(DGRAD, INNER_SINGLE, ddelta, Wdt_c)):
+                dx_dbl[g][:, :R] = t                   # (a strided `out=` is an untuned GEMM shape class: pathologically slow by default)
+            dWdt = product(WGRAD, INNER_SINGLE, ddelta, [t[:, :R] for t in x_dbl])    # [Din, R]; the dt columns of x_dbl in place (leading dimension R + 2N)
+        dWx = product(WGRAD, inner, dx_dbl, [t.view(M, Din) for t in xc])                                        # [R+2N, Din] fp32 each
         if hip_ops.conv_xproj_bwd_supported(xz[0][..., :Din], Wx_c[0], S, cw[0].shape[-1], du[0], dx_dbl[0]):
             # d x~ = du + dx_dbl @ Wx is formed tile by tile inside the conv backward (K4x) instead of by an addmm over [M, Din]
             merged_dx = hip_ops.DX_MERGED and cw[0].shape[-1] == 4      # one direction: dx straight into d(xz), no copy pass
@@ -613,11 +353,7 @@ class _SpiralSSMFn(torch.autograd.Function):
                                                                    merged_out=dxz[g][..., :Din] if merged_dx else None))
         else:
             merged_dx = False
-            if _inner_on_own(G, M, dx_dbl[0], Wx_c[0], True, False):
-                _own_pair(dx_dbl, Wx_c, True, False, du.view(G, M, Din), accumulate=True)    # d x~ = du + dx_dbl @ Wx, in place, one launch
-            else:
-                for g in each:      # in place: an out-of-place addmm first copies `du` into its result (a 2 x 308 MB device memcpy per call)
-                    GemmChain.run(du[g].view(M, Din).addmm_, dx_dbl[g], Wx_c[g])
+            product(DGRAD, inner, dx_dbl, Wx_c, out=du.view(G, M, Din), accumulate=True)    # d x~ = du + dx_dbl @ Wx, in place
             cres = stage(lambda g: hip_ops.gather_conv1d_bwd(xz[g][..., :Din], cw[g], cb[g], du[g], row_index=idx[g], ndir=ndir, silu=True))
         if not merged_dx:                                          # K4x already summed the directions into dxz[..., :Din]
             stage(lambda g: hip_ops.token_merge(cres[g][0].view(ndir, Bsz, L, Din), out=dxz[g][..., :Din]))
@@ -853,16 +589,16 @@ class _GateDefer:
 
 def _gate_in_dgrad_rule(on_gpu, dtype, autocast_dtype, contiguous, wants_grad, xz_shape, w_shape):
     """The routing rule on plain values (so that it can be checked without a device): the switches; 16-bit activations that autocast
-    would not change; a backward to come; and the shape test of _linear_dgrad for dy [M, K = d_model] @ wt [N = d_inner, K]^T -- at
-    least LARGE_MIN_ROWS rows (above the small-launch kernel's range), K12's column rule, a shape K12 takes."""
-    if not (hip_ops.GATE_IN_DGRAD and HOIST_GATE and LARGE_DGRAD_NT and hip_ops.GEMM_LARGE):
+    would not change; a backward to come; and the shape test of projections.route for the input gradient dy [M, K = d_model] @ wt
+    [N = d_inner, K]^T -- K12's shape rule (projections.large_shape), rows above the small-launch kernel's window, a shape K12 takes."""
+    if not (hip_ops.GATE_IN_DGRAD and HOIST_GATE and proj.LARGE_DGRAD_NT and hip_ops.GEMM_LARGE):
         return False
     if not (on_gpu and len(xz_shape) == 3 and contiguous and wants_grad and dtype in (torch.bfloat16, torch.float16)):
         return False
     if autocast_dtype is not None and autocast_dtype != dtype:
         return False
     M, N, K = xz_shape[0] * xz_shape[1], w_shape[1], w_shape[0]
-    if N * 2 != xz_shape[2] or M < LARGE_MIN_ROWS or N < LARGE_MIN_COLS or (N < 1024 and K > LARGE_MAX_K_NARROW) or M <= PAIR_OWN_MAX_ROWS:
+    if N * 2 != xz_shape[2] or not proj.large_shape(M, N, K) or proj.own_rows(SINGLE, M):
         return False
     code = {torch.bfloat16: _lib.DM_BF16, torch.float16: _lib.DM_F16}[dtype]
     return bool(_lib.load().dm_gemm_large_gated_supported(M, N, K, code))
@@ -885,10 +621,7 @@ class _GatedOutProjFn(torch.autograd.Function):
         wc = cast_weight(weight, y.dtype)
         ctx.save_for_backward(y, pre, xz, wc)
         ctx.defer, ctx.w_dt = defer, weight.dtype
-        y2 = y.reshape(-1, y.shape[-1])
-        if _own_large(y2, wc):
-            return hip_ops.gemm_large(y2, wc).view(*y.shape[:-1], wc.shape[0])
-        return GemmChain.run(F.linear, y, wc, None)
+        return product(FWD, SINGLE, y, wc)
 
     @staticmethod
     def backward(ctx, dout):
@@ -906,9 +639,9 @@ class _GatedOutProjFn(torch.autograd.Function):
             if hip_ops.gemm_large_gated_supported(dy2c, wt, z2, pre2, dz2):
                 g = hip_ops.gemm_large_gated(dy2c, wt, z2, pre2, dz2).view(Bsz, L, Din)
             else:       # (a gradient layout that K12 does not take: the two launches, into the same buffers)
-                dy = _linear_dgrad(dy2, dy2c, wc, True).view(Bsz, L, Din)
+                dy = product(DGRAD, SINGLE, dy2c, wc, a_strided=dy2).view(Bsz, L, Din)
                 g = hip_ops.gate_bwd(dy, xz[..., Din:], pre, dz_out=dxz[0][..., Din:])[0]
-            dw = _linear_wgrad(dy2c, y.reshape(-1, Din).contiguous(), True).to(ctx.w_dt) if ctx.needs_input_grad[3] else None
+            dw = product(WGRAD, SINGLE, dy2c, y.reshape(-1, Din).contiguous()).to(ctx.w_dt) if ctx.needs_input_grad[3] else None
             ctx.defer.dxz = dxz
         return None, g, None, dw, None
 

@@ -5,7 +5,7 @@ step is bound by the launch rate (eager) or by per-node dispatch (hipGraph repla
   * `A = -exp(A_log)` (exp, neg; mul, neg in the backward)         -- 32 mixers x ~5 launches
   * the autocast copies of the projection weights (in_proj, x_proj, dt_proj, out_proj, the fusion MLP)   -- ~160 cast launches
 `prepare(model)` does both for the WHOLE model at the top of `DiffMa.forward` with foreach kernels: the mixers pick their `A` from
-`_A_step`, and `shadow_of(weight, dtype)` hands the 16-bit copy to `_LinearSplitKFn` / `_SpiralSSMFn` as long as the master has not
+`_A_step`, and `shadow_of(weight, dtype)` hands the 16-bit copy to `projections._LinearSplitKFn` / `_SpiralSSMFn` as long as the master has not
 been written since (its `_version` is compared: a stale or unknown weight falls back to the per-call cast, so nothing depends on
 `prepare` having run).  Inside a captured training step the foreach launches are part of the graph and run on every replay.
 """

@@ -136,7 +136,7 @@ def test_routing_rule_condition_by_condition(monkeypatch):
     the other way does not: each switch, fp32, a host tensor, an autocast dtype that differs, no backward, a strided xz, fewer rows
     than LARGE_MIN_ROWS, an out_proj narrower than LARGE_MIN_COLS, a width K12 does not take, a contraction it does not take, an xz
     that is not [.., 2 d_inner]."""
-    from diffma_amd import hip_ops, selective_scan_interface as ssi
+    from diffma_amd import hip_ops, projections as proj, selective_scan_interface as ssi
 
     monkeypatch.setattr(hip_ops, "GATE_IN_DGRAD", True)
     base = dict(on_gpu=True, dtype=BF16, autocast_dtype=BF16, contiguous=True, wants_grad=True, xz_shape=(512, 196, 2048), w_shape=(512, 1024))
@@ -148,10 +148,10 @@ def test_routing_rule_condition_by_condition(monkeypatch):
                dict(xz_shape=(512, 196, 2000), w_shape=(512, 1000)), dict(w_shape=(576, 1024)), dict(xz_shape=(512, 196, 4096)),
                dict(xz_shape=(512 * 196, 2048))):
         assert not rule(**kw), kw
-    for mod, name in ((hip_ops, "GATE_IN_DGRAD"), (ssi, "HOIST_GATE"), (ssi, "LARGE_DGRAD_NT"), (hip_ops, "GEMM_LARGE")):
+    for mod, name in ((hip_ops, "GATE_IN_DGRAD"), (ssi, "HOIST_GATE"), (proj, "LARGE_DGRAD_NT"), (hip_ops, "GEMM_LARGE")):
         with monkeypatch.context() as mp:
             mp.setattr(mod, name, False)
             assert not rule(), name
-    assert ssi.LARGE_MIN_ROWS > ssi.PAIR_OWN_MAX_ROWS                   # the small-launch kernel's range lies below the path
+    assert proj.LARGE_MIN_ROWS > proj.PAIR_OWN_MAX_ROWS                   # the small-launch kernel's range lies below the path
     xz = torch.zeros(64, 196, 2048, dtype=BF16, requires_grad=True)    # the tensor form: a host tensor never takes it
     assert not ssi.gate_in_dgrad_wanted(xz, torch.zeros(512, 1024))

@@ -569,12 +569,12 @@ def test_linear_splitk_runs_dm_gemm_at_the_mamba2_width(gpu, monkeypatch, dt):
     master weight, autocast: the forward and both gradients run on dm_gemm (three single launches), each within the section-2
     bounds of fp64 autograd on the rounded operands; W.grad is the kernel's fp32 output (the cast to the weight dtype is fp32 to
     fp32)."""
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
     names = _record(monkeypatch)
     (x, W, _), dy, r = _linear_case(gpu, 196, 512, 2096, dt, 11)
     with torch.autocast("cuda", dtype=dt):
-        y = ssi.linear_splitk(x, W)
+        y = proj.linear_splitk(x, W)
     y.backward(dy)
     torch.cuda.synchronize()
     assert names == [("single", "dm_gemm")] * 3, names
@@ -589,15 +589,15 @@ def test_linear_splitk_leaves_dm_gemm_alone_outside_its_gate(gpu, monkeypatch, d
     """The same call with 63 rows, with PAIR_OWN_MAX_ROWS + 1 rows, with a bias, and at a width that is not a multiple of 8 records
     no dm_gemm; the library computes the products (fp32 accumulation, 16-bit results, at most one more rounding of W.grad to 16
     bits), so the 16-bit bound of section 2 holds for all three."""
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
-    rows = {"rows63": 63, "rows_max_plus_1": ssi.PAIR_OWN_MAX_ROWS + 1}.get(case, 196)
+    rows = {"rows63": 63, "rows_max_plus_1": proj.PAIR_OWN_MAX_ROWS + 1}.get(case, 196)
     N = 2090 if case == "width2090" else 2096
     bias = case == "bias"
     names = _record(monkeypatch)
     (x, W, b), dy, r = _linear_case(gpu, rows, 512, N, dt, 12, bias)
     with torch.autocast("cuda", dtype=dt):
-        y = ssi.linear_splitk(x, W, b)
+        y = proj.linear_splitk(x, W, b)
     y.backward(dy)
     torch.cuda.synchronize()
     assert not [n for n in names if n[1].startswith("dm_gemm")], names
@@ -610,14 +610,14 @@ def test_linear_splitk_leaves_dm_gemm_alone_outside_its_gate(gpu, monkeypatch, d
 def test_linear_pair_runs_dm_gemm_n_and_equals_linear_splitk(gpu, monkeypatch, dt):
     """linear_pair on two [1, 196, 512] inputs and two [2048, 512] fp32 weights: three dm_gemm launches through the `_n` entry,
     every output and gradient within the bounds and bit for bit that of linear_splitk on that mixer alone."""
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
     names = _record(monkeypatch)
     cases = [_linear_case(gpu, 196, 512, 2048, dt, 20 + k) for k in (0, 1)]
     (x0, W0, _), dy0, _ = cases[0]
     (x1, W1, _), dy1, _ = cases[1]
     with torch.autocast("cuda", dtype=dt):
-        y0, y1 = ssi.linear_pair(x0, x1, W0, W1)
+        y0, y1 = proj.linear_pair(x0, x1, W0, W1)
     torch.autograd.backward([y0, y1], [dy0, dy1])
     torch.cuda.synchronize()
     assert [n for n in names if n[1] == "dm_gemm"] == [("n", "dm_gemm")] * 3, names
@@ -625,7 +625,7 @@ def test_linear_pair_runs_dm_gemm_n_and_equals_linear_splitk(gpu, monkeypatch, d
         _linear_verify(f"pair {k}", dt, r, y, x.grad, W.grad, 196, 512, 2048, F32)
         xs, Ws = x.detach().clone().requires_grad_(True), W.detach().clone().requires_grad_(True)
         with torch.autocast("cuda", dtype=dt):
-            ys = ssi.linear_splitk(xs, Ws)
+            ys = proj.linear_splitk(xs, Ws)
         ys.backward(dy)
         torch.cuda.synchronize()
         assert torch.equal(ys, y) and torch.equal(xs.grad, x.grad) and torch.equal(Ws.grad, W.grad), k
@@ -634,7 +634,7 @@ def test_linear_pair_runs_dm_gemm_n_and_equals_linear_splitk(gpu, monkeypatch, d
 def test_own_pair_accumulates_in_place_at_the_x_proj_shape(gpu, monkeypatch):
     """du += dx_dbl @ Wx for both mixers in one launch (dx_dbl [2, 588, 64], Wx [2, 64, 1024], du [2, 588, 1024], bf16): per element
     within the accumulate bound."""
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
     names = _record(monkeypatch)
     g = torch.Generator().manual_seed(31)
@@ -642,7 +642,7 @@ def test_own_pair_accumulates_in_place_at_the_x_proj_shape(gpu, monkeypatch):
     Wx = (torch.randn(2, 64, 1024, generator=g) * 0.1).to(BF16)
     du0 = torch.randn(2, 588, 1024, generator=g).to(BF16)
     du = du0.to(gpu)
-    out = ssi._own_pair(dxd.to(gpu), Wx.to(gpu), True, False, du, accumulate=True)
+    out = proj._own_pair(dxd.to(gpu), Wx.to(gpu), True, False, du, accumulate=True)
     torch.cuda.synchronize()
     assert names == [("n", "dm_gemm")] and out.data_ptr() == du.data_ptr()
     for k in (0, 1):

@@ -323,7 +323,7 @@ def test_step_prep_shadows_survive_two_forwards_and_a_retained_graph():
     with a live graph -> new buffers; changed masters with no live graph -> in place (the steady state of a training loop)."""
     from diffma_amd import step_prep
     from diffma_amd.mamba import Mamba
-    from diffma_amd.selective_scan_interface import linear_splitk
+    from diffma_amd.projections import linear_splitk
 
     torch.manual_seed(0)
     m = torch.nn.Sequential(Mamba(32, d_state=16))      # prepare() takes the MODEL (its plan holds the mixers, not the model itself)

@@ -1767,24 +1767,24 @@ def test_linear_splitk_takes_the_large_kernel_and_matches_autograd(gpu, monkeypa
     """linear_splitk at the bench's row count: the forward and the input gradient run on K12 (the latter through the transposed
     weight copy), the weight gradient on the split-K product -- all three against fp64 autograd of the same 16-bit operands."""
     from diffma_amd import _lib
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
     names = []
     real = _lib.call
     monkeypatch.setattr(_lib, "call", lambda n, a, st: (names.append(n), real(n, a, st))[1])
     g = torch.Generator(device=gpu).manual_seed(3)
     M = 16384
-    # the default policy of selective_scan_interface._own_large (outputs of 1024 columns and more): in_proj forward and out_proj input
+    # the default policy of projections.route (outputs of 1024 columns and more): in_proj forward and out_proj input
     # gradient on K12, the two 512-column products on the library's NT kernels; with DIFFMA_GEMM_LARGE_MIN_COLS=512 all but the
     # in_proj input gradient (contraction 2048)
-    monkeypatch.setattr(ssi, "LARGE_MIN_COLS", cols)
+    monkeypatch.setattr(proj, "LARGE_MIN_COLS", cols)
     for K, N, want in ((512, 2048, 1), (1024, 512, 1 if cols == 1024 else 2)):
         x = (torch.randn(M, K, device=gpu, generator=g)).bfloat16().requires_grad_(True)
         W = (torch.randn(N, K, device=gpu, generator=g) * K ** -0.5).requires_grad_(True)       # fp32 master
         dy = torch.randn(M, N, device=gpu, generator=g).bfloat16()
         names.clear()
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            y = ssi.linear_splitk(x, W)
+            y = proj.linear_splitk(x, W)
         y.backward(dy)
         assert names.count("dm_gemm_large") == want, names
         x64, W64 = x.detach().double().requires_grad_(True), W.detach().bfloat16().double().requires_grad_(True)

@@ -1142,12 +1142,12 @@ def test_full_width_mixer_takes_the_fused_dtproj_backward(gpu, monkeypatch):
 def test_small_batch_weight_gradient_gemm_writes_fp32(gpu):
     """Below the split-K threshold the weight-gradient product a^T b leaves the GEMM in fp32 (aten::mm.dtype) instead of as a 16-bit
     result + cast launch: fp32 result, at least as close to the fp64 product as the rounded form."""
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
 
     g = torch.Generator().manual_seed(5)
     a = torch.randn(1568, 96, generator=g).bfloat16().to(gpu)
     b = torch.randn(1568, 512, generator=g).bfloat16().to(gpu)
-    got = ssi._tn_splitk_impl(a, b)
+    got = proj._tn_splitk_impl(a, b)
     ref = a.double().t() @ b.double()
     rounded = (a.t() @ b).float()
     assert got.dtype == torch.float32 and got.shape == (96, 512)
@@ -1214,11 +1214,12 @@ def test_spiral_pair_equals_two_single_operators_bit_for_bit_on_library_projecti
     so both outputs and every gradient are EQUAL, and the pair makes fewer C-ABI calls.  spiral(8): L = 64 is the smallest length on
     the chunk-parallel scans; d_model 256 (Din 512, dt_rank 16) the smallest width dm_dtproj_bwd takes."""
     from diffma_amd import _lib
+    from diffma_amd import projections as proj
     from diffma_amd import selective_scan_interface as ssi
     from diffma_amd.mamba import Mamba
     from diffma_amd.tools import spiral
 
-    monkeypatch.setattr(ssi, "PAIR_OWN_MAX_ROWS", 0)
+    monkeypatch.setattr(proj, "PAIR_OWN_MAX_ROWS", 0)
     torch.manual_seed(7)
     n, B, d_model = 8, 1, 256
     orders, inverses = spiral(n)
@@ -1282,7 +1283,7 @@ def test_bench_dispatch_end_to_end_matches_oracle(gpu, monkeypatch):
     gradients are summed over the chunks; it is the checker, not the path).  Bounds: output rel-L2 <= 8e-3, every parameter gradient
     rel-L2 <= 4e-2 (bf16 activations, fp32 master weights): twice the measured worst case, which the assert message reports."""
     from diffma_amd import _lib, hip_ops
-    from diffma_amd import selective_scan_interface as ssi
+    from diffma_amd import projections as proj
     from diffma_amd.diffusion import create_diffusion
     from diffma_amd.model import DiffMa
     from oracle.model_ref import diffma_forward_ref
@@ -1301,8 +1302,8 @@ def test_bench_dispatch_end_to_end_matches_oracle(gpu, monkeypatch):
     monkeypatch.setattr(_lib, "call", call)
     monkeypatch.setattr(_lib, "call_n", call_n)
     tn = []
-    real_tn = ssi._tn_splitk_impl
-    monkeypatch.setattr(ssi, "_tn_splitk_impl", lambda a, b: (tn.append((a.shape[0], a.shape[1], b.shape[1])), real_tn(a, b))[1])
+    real_tn = proj._tn_splitk_impl
+    monkeypatch.setattr(proj, "_tn_splitk_impl", lambda a, b: (tn.append((a.shape[0], a.shape[1], b.shape[1])), real_tn(a, b))[1])
 
     torch.manual_seed(11)
     depth, B, L = 2, 176, 196

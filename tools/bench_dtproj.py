@@ -30,7 +30,7 @@ for S in [int(a) for a in sys.argv[1:]] or [24, 192, 768, 1536]:
     print(f"variant {os.environ.get('DM_DTP_VARIANT', '0')} nseq {S}: dtproj_softplus {us:.1f} us {nb / us / 1e3:.0f} GB/s | F.linear {us_lib:.1f} us", flush=True)
 
 # backward: dm_dtproj_bwd (one read of ddelta) against the two library products it replaces
-from diffma_amd.selective_scan_interface import _tn_splitk  # noqa: E402
+from diffma_amd.projections import _tn_splitk  # noqa: E402
 for S in [int(a) for a in sys.argv[1:]] or [24, 192, 768, 1536]:
     M, Dm, R, P = S * 196, 1024, 32, 64
     if M % 32:
