@@ -25,3 +25,9 @@ extern "C" int dm_scan_bwd_launch_group_channels(int nseq, int dim, int seqlen, 
     if (dm::bwd_chunked_lc(nseq, dim, seqlen, dstate, flags) > 0) return dm::WAVE;
     return dm_scan_bwd_group_channels(dstate);
 }
+
+// tokens per segment of the chunk-parallel backward (scan_bwd_chunked.h) when a launch of this size -- with arguments the family
+// accepts -- takes it; 0 when it takes the sequential kernel.  The backward twin of dm_scan_fwd_launch_segment.
+extern "C" int dm_scan_bwd_launch_segment(int nseq, int dim, int seqlen, int dstate, int flags) {
+    return dm::bwd_chunked_segment(nseq, dim, seqlen, dstate, flags);
+}

@@ -250,7 +250,7 @@ def _variant_flag(variant):
 # (only where it reaches 1.1 x the sequential kernel): up to 512 channel-waves, 256 with checkpoints.  Kernel alone, bf16, dim 1024,
 # nseq 3 / 15 / 24: 63 -> 31, 67 -> 32, 71 -> 59 us at L 256 and 262 -> 116, 266 -> 121, 276 -> 232 us at L 1024; the graphed batch-1
 # denoiser call of DiffMa-L/2 4.20 -> 2.66 ms at 256 tokens and 10.55 -> 4.27 ms at 1024 (profiles/scan_fwd_chunked_long.json;
-# tools/scan_variants.py --forward-only --seqlen L).  The backward stays on the sequential kernel past 196 tokens.
+# tools/scan_variants.py --forward-only --seqlen L).  The backward past 196 tokens has its own switch, SCAN_BWD_CHUNKED_LONG below.
 # DIFFMA_SCAN_CHUNKED_LONG=0 returns those forward launches to the sequential kernel (A/B runs, and the way back).
 SCAN_CHUNKED_LONG = os.environ.get("DIFFMA_SCAN_CHUNKED_LONG", "1") == "1"
 SCAN_CHUNKED_SEGMENT = 196          # tokens one segment holds: longer forward launches are the ones the switch above covers
@@ -269,6 +269,32 @@ def scan_fwd_segment(S, Dm, L, N, flags=0):
     tokens, 140 past that), or 0 where it takes the sequential kernel (dm_scan_fwd_launch_segment: sizes only, no device; a launch
     without checkpoints -- one that writes them past 196 tokens is taken up to 256 channel-waves instead of 512)."""
     return int(_lib.load().dm_scan_fwd_launch_segment(S, Dm, L, N, flags))
+
+
+# The chunk-parallel backward past one segment (csrc/scan_bwd_chunked.h: 196 < L <= 1024, walked from the last segment of 196 tokens
+# to the first with the adjoint carry handed on through LDS).  The library takes it for small launches by the same routing rule
+# (only where the kernel alone reaches 1.1 x the sequential one): up to 256 channel-waves, one round of workgroups.  Kernel alone,
+# bf16, dim 1024, nseq 3 / 15 / 24: 147 -> 71, 149 -> 76, 150 -> 144 us at L 256 and 582 -> 235, 579 -> 253, 583 -> 497 us at L 1024
+# (1.04 x and 1.17 x at nseq 24 = 384 channel-waves: not routed); the graphed one-sample training step of DiffMa-L/2 10.80 -> 7.30 ms
+# at 256 tokens and 28.18 -> 13.48 ms at 1024 (profiles/scan_bwd_chunked_long.json; tools/scan_variants.py --seqlen L --train-step SIZE).
+# DIFFMA_SCAN_BWD_CHUNKED_LONG=0 returns those backward launches to the sequential kernel (A/B runs, and the way back); the
+# forward's switch above is independent of it.
+SCAN_BWD_CHUNKED_LONG = os.environ.get("DIFFMA_SCAN_BWD_CHUNKED_LONG", "1") == "1"
+
+
+def _scan_bwd_variant_flag(L, variant):
+    """_variant_flag for a backward launch of L tokens: with SCAN_BWD_CHUNKED_LONG off, launches the library would choose for itself
+    (variant None) carry DM_FLAG_SCAN_SEQUENTIAL past one segment."""
+    if variant is None and not SCAN_BWD_CHUNKED_LONG and L > SCAN_CHUNKED_SEGMENT:
+        return DM_FLAG_SCAN_SEQUENTIAL
+    return _variant_flag(variant)
+
+
+def scan_bwd_segment(S, Dm, L, N, flags=0):
+    """Tokens per segment of the chunk-parallel backward that a launch [S, L, Dm] at d_state N with these flags takes (56 or 196 for
+    the one-segment launches up to 196 tokens, 196 past that), or 0 where it takes the sequential kernel
+    (dm_scan_bwd_launch_segment: sizes only, no device)."""
+    return int(_lib.load().dm_scan_bwd_launch_segment(S, Dm, L, N, flags))
 
 
 def _scan_args(a, u, delta, A, Bm, Cm, D, z, delta_bias, delta_softplus, delta_activated, z_row_index, out_row_index, batch_per_dir,
@@ -371,7 +397,8 @@ def scan_bwd(u, delta, A, Bm, Cm, D, z, delta_bias, dout, ckpt, delta_softplus=T
     N = A.shape[1]
     A32, D32, b32 = _f32c(A), _f32c(D), _f32c(delta_bias)
     a = _scan_args(dm_scan_bwd_args(), u, delta, A32, Bm, Cm, D32, z, b32, delta_softplus, delta_activated, z_row_index, out_row_index,
-                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, variant, DM_FLAG_DOUT_PER_SEQ if dout_per_seq else 0)
+                   batch_per_dir, ckpt, ckpt_every, ngroups, a_shared, None,
+                   _scan_bwd_variant_flag(L, variant) | (DM_FLAG_DOUT_PER_SEQ if dout_per_seq else 0))
     dbc_shape = scan_bwd_partial_shape(S, L, Dm, N, a.flags)   # a row per 256 / SPLIT channels (sequential kernel) or per 64 (chunk-parallel, small launches)
     nw = dbc_shape[2]
     dev = u.device

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 35
+#define DM_ABI_VERSION 36
 
 typedef enum {
     DM_OK = 0,
@@ -54,8 +54,9 @@ enum {
                                    [batch_per_dir][row][d] shared by the directions  */
     DM_FLAG_SCAN_SEQUENTIAL = 16, /* scan fwd / bwd: take the sequential-in-time kernel whatever the launch size          */
     DM_FLAG_SCAN_CHUNKED = 32,  /* scan fwd / bwd: take the chunk-parallel (two-pass) kernel where it is instantiated: the
-                                   forward for 56 < seqlen <= 1024 (past 196 tokens in segments, ABI 35), the backward up to
-                                   196 tokens (longer ones stay on the sequential kernel, which reads the same checkpoints).
+                                   forward for 56 < seqlen <= 1024 (past 196 tokens in segments, ABI 35), the backward for
+                                   16 < seqlen <= 1024 (past 196 tokens in segments, ABI 36); longer launches stay on the
+                                   sequential kernels.  Either backward reads the checkpoints of either forward.
                                    By default the library chooses by launch size (small launches are latency-bound)       */
     DM_FLAG_OUT_ACCUMULATE = 64, /* scan fwd with row indices: out[s][out_row_index[l]] += y (read-add-store) instead of = y.
                                    The caller walks the directions of the CrossMerge (block/mamba.py:59-69) with one launch
@@ -242,6 +243,11 @@ int dm_scan_fwd_launch_segment(int nseq, int dim, int seqlen, int dstate, int fl
  * 2 KB at 32, 8 KB at 64, 32 KB at 128.  DM_FLAG_A_SHARED selects the one-exp form at d_state 16, 64 and 128 for the Mamba-2
  * call pattern (z, row indices, DM_FLAG_DELTA_SOFTPLUS; used with DM_FLAG_DOUT_PER_SEQ); DM_FLAG_DELTA_ACTIVATED and the
  * chunk-parallel kernel are d_state 16 only.  A build with -DDM_FAST_BUILD has d_state 16 only.
+ *
+ * Kernel family: small launches at d_state 16 take the chunk-parallel kernel for 16 < seqlen <= 1024 -- one segment up to 196
+ * tokens, ceil(seqlen / 196) segments of 196 tokens walked from the last to the first past that (ABI 36) -- and everything else
+ * the sequential one; dm_scan_bwd_launch_segment answers which, dm_scan_bwd_launch_group_channels sizes dBC_partial for it, and
+ * two congruent structs given to dm_selective_scan_bwd_n share one launch exactly where the query answers non-zero.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t nseq, dim, seqlen, dstate;
@@ -283,6 +289,16 @@ int dm_scan_bwd_group_channels(int dstate);   /* GC of the sequential kernel; <=
  * 64 channels), each owning a run of time steps, two passes joined by the linearity of the adjoint carry -- which writes
  * one dB/dC partial row per 64 channels; size dBC_partial with this value. */
 int dm_scan_bwd_launch_group_channels(int nseq, int dim, int seqlen, int dstate, int flags);
+/* Host-only query (ABI 36), the backward twin of dm_scan_fwd_launch_segment: which kernel a backward launch of this size takes.
+ * 0: the sequential kernel.  Otherwise the tokens per segment G of the chunk-parallel instantiation chosen, NW = 7 waves per
+ * (sequence, 64 channels) each owning G / 7 consecutive steps of a segment: 56 for 16 < seqlen <= 56 and 196 for 56 < seqlen <= 196
+ * (one segment), 196 for 196 < seqlen <= 1024, which walk ceil(seqlen / 196) segments from the last to the first and hand the
+ * fp32 adjoint carry from one to the next.  The launch meant is one with arguments the family accepts (d_state 16, fp32 or
+ * I/O-dtype B/C); flags may carry DM_FLAG_SCAN_SEQUENTIAL / DM_FLAG_SCAN_CHUNKED.  Unforced, the library takes the family up to
+ * 512 channel-waves (nseq * ceil(dim / 64)) up to 196 tokens and up to 256 past that (one round of workgroups: measured 1.96-2.48 x
+ * the sequential kernel there, 1.03-1.17 x in the second round, profiles/scan_bwd_chunked_long.json).  Non-zero exactly where
+ * dm_scan_bwd_launch_group_channels answers 64 and where dm_selective_scan_bwd_n pairs two congruent structs. */
+int dm_scan_bwd_launch_segment(int nseq, int dim, int seqlen, int dstate, int flags);
 
 /* ------------------------------------------------------------------------------------------------
  * Token gather + causal depthwise conv1d (+bias, +SiLU), forward.  Replaces

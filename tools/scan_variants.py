@@ -4,13 +4,19 @@ through row-index tables, no z, delta already activated, checkpoints for the bac
 launch): the two variants alternate launch by launch in one process, and every figure is the median over --iters timed launches
 after --warmup untimed ones, with the spread (min, 10th and 90th percentile, max) beside it.
 
-The forward is chunk-parallel up to 1024 tokens (one segment up to 196, segments of dm_scan_fwd_launch_segment tokens past that); the
-backward only up to 196, so past 196 tokens no "chunked" backward is reported (K2 reads the same checkpoints whichever forward
-wrote them).
+Both scans are chunk-parallel up to 1024 tokens: one segment up to 196, segments of dm_scan_fwd_launch_segment /
+dm_scan_bwd_launch_segment tokens past that.  A "chunked" arm is timed wherever the forced query answers for it; the backward reads
+the checkpoints of the sequential forward in both arms (either forward writes the same slots).
+
+--sample-step SIZE times the graphed and the eager batch-1 denoiser call of DiffMa-L/2 at input_size SIZE with the forward's switch
+(DIFFMA_SCAN_CHUNKED_LONG) on and off, --train-step SIZE the graphed one-sample training step with the backward's switch
+(DIFFMA_SCAN_BWD_CHUNKED_LONG) on and off; the two arms alternate call by call in one process and are compared with each other.
 
   python tools/scan_variants.py [--nseq 1536 768 96 24] [--iters 10]  > profiles/r04_scan_variants.txt
   python tools/scan_variants.py --forward-only --seqlen 256 1024 --dim 1024 2048 --nseq 3 24 96 192 --iters 50 \
          --sample-step 32 64 --json profiles/scan_fwd_chunked_long.json
+  python tools/scan_variants.py --seqlen 256 1024 --dim 1024 2048 --nseq 3 6 15 24 48 96 --iters 50 \
+         --train-step 32 64 --json profiles/scan_bwd_chunked_long.json
 """
 import argparse
 import json
@@ -83,6 +89,10 @@ def scan_rows(a, dev):
                     for v in bwd_variants:
                         row[f"bwd_{v}_us"] = t[v]["median"]
                         row[f"bwd_{v}_spread"] = t[v]
+                    row["bwd_segment"] = hip_ops.scan_bwd_segment(S, Dm, L, N, _lib.DM_FLAG_SCAN_CHUNKED)
+                    row["bwd_routed_chunked"] = hip_ops.scan_bwd_segment(S, Dm, L, N, 0) > 0
+                    if "chunked" in t:
+                        row["bwd_speedup"] = round(t["sequential"]["median"] / t["chunked"]["median"], 3)
                 del ckpt
                 print(json.dumps(row), flush=True)
                 rows.append(row)
@@ -133,6 +143,57 @@ def sample_step_rows(a, dev):
     return rows
 
 
+def train_step_rows(a, dev):
+    """The graphed one-sample training step of DiffMa-L/2 under bf16 autocast (graphed.GraphedTrainStep: noise, forward, loss, backward,
+    fused AdamW, EMA in one hipGraph), captured once with the chunk-parallel backward past 196 tokens on and once with it off
+    (hip_ops.SCAN_BWD_CHUNKED_LONG = DIFFMA_SCAN_BWD_CHUNKED_LONG; the flag word is fixed at capture).  Each arm steps its own copy
+    of the model; the replays alternate."""
+    import copy
+
+    from diffma_amd.diffusion import create_diffusion
+    from diffma_amd.graphed import GraphedTrainStep
+    from diffma_amd.model import DiffMa_models
+
+    rows = []
+    diffusion = create_diffusion("")
+    for size in a.train_step:
+        L = (size // 2) ** 2
+        g = torch.Generator(device=dev).manual_seed(size)
+        mk = lambda *s: torch.randn(*s, device=dev, generator=g)
+        z, y, y2, w = mk(1, 4, size, size), mk(1, 512), mk(1, L, 512), torch.sigmoid(mk(1, L, 1))
+        t = torch.tensor([500], device=dev)
+        steps = {}
+        for on in (True, False):
+            hip_ops.SCAN_BWD_CHUNKED_LONG = on
+            torch.manual_seed(size)
+            model = DiffMa_models["DiffMa-L/2"](input_size=size).to(dev).train()
+            ema = copy.deepcopy(model).requires_grad_(False)
+            opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=0, fused=True, capturable=True)
+            steps[on] = GraphedTrainStep(model, ema, opt, diffusion, z, t, y, y2, w, autocast_dtype=torch.bfloat16, ema_decay=0.999)
+        hip_ops.SCAN_BWD_CHUNKED_LONG = True
+        times = {True: [], False: []}
+        for i in range(a.warmup + a.iters):
+            for on in (True, False):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                steps[on].step(z, t, y, y2, w)
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= a.warmup:
+                    times[on].append(1e3 * e0.elapsed_time(e1))
+        d_inner = 2 * 1024
+        row = dict(model="DiffMa-L/2", input_size=size, L=L, batch=1, dtype="bf16 autocast", mode="graphed training step",
+                   bwd_segment=hip_ops.scan_bwd_segment(3, d_inner, L, 16, 0),
+                   graph_bwd_chunked_long_us=spread(times[True]), graph_bwd_sequential_us=spread(times[False]))
+        row["graph_speedup"] = round(row["graph_bwd_sequential_us"]["median"] / row["graph_bwd_chunked_long_us"]["median"], 3)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        del steps
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nseq", type=int, nargs="+", default=[1536, 768, 96, 24])
@@ -140,15 +201,17 @@ def main():
     ap.add_argument("--dim", type=int, nargs="+", default=[1024])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--forward-only", action="store_true", help="time the forward alone (the only chunk-parallel scan past 196 tokens)")
+    ap.add_argument("--forward-only", action="store_true", help="time the forward alone")
     ap.add_argument("--sample-step", type=int, nargs="*", default=[], metavar="INPUT_SIZE",
                     help="also time one batch-1 DiffMa-L/2 denoiser call at these input sizes, DIFFMA_SCAN_CHUNKED_LONG on against off")
+    ap.add_argument("--train-step", type=int, nargs="*", default=[], metavar="INPUT_SIZE",
+                    help="also time the graphed one-sample DiffMa-L/2 training step at these input sizes, DIFFMA_SCAN_BWD_CHUNKED_LONG on against off")
     ap.add_argument("--json", default=None, help="write everything to this file as one JSON document")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     doc = dict(device=torch.cuda.get_device_name(0), iters=a.iters, warmup=a.warmup,
                note="kernel times in us from device events around the C-ABI launch, variants alternating in one process",
-               scans=scan_rows(a, dev), sample_step=sample_step_rows(a, dev))
+               scans=scan_rows(a, dev), sample_step=sample_step_rows(a, dev), train_step=train_step_rows(a, dev))
     if a.json:
         with open(a.json, "w") as f:
             json.dump(doc, f, indent=1)
