@@ -14,6 +14,12 @@
 // found_inf (device scalar, GradScaler's convention; the graphed step computes it from the all-reduced gradients): != 0 leaves p, m, v
 // and the counters alone; the EMA still moves towards the unchanged weights when ema_on_skip is set (this repository's graphed
 // step, graphed.py) and is left alone otherwise (the reference's eager loop `continue`s before update_ema, train.py:254-256).
+// grad_scale (device scalar or NULL; the fp16 step's loss scale, reference train.py:95,247-263): the gradients in memory are
+// grad_scale times the true ones; each is divided by it on its way into the moments -- torch's `grad /= (double)*grad_scale_ptr`: a
+// double quotient rounded once to fp32 -- and is not written back (still 36 bytes per element).  found_inf is computed from the scaled
+// gradients (dm_grads_nonfinite) and means what it meant.
+// dm_loss_scale_update -- torch._amp_update_scale_ (aten/src/ATen/native/cuda/AmpKernels.cu) as one launch of one wave: back-off on
+// found_inf, growth after growth_interval clean steps unless the grown scale would be infinite, and the count of skipped steps.
 #include "dm_common.h"
 
 namespace dm {
@@ -34,7 +40,7 @@ __global__ __launch_bounds__(64) void adamw_steps_kernel(const dm_adamw_args p) 
 // evaluated in double and rounded to fp32 once on assignment, exactly as there (the kernel is HBM-bound; the fp64 pipe is idle anyway)
 template <bool VEC>
 __device__ __forceinline__ void adamw_elems(const dm_adamw_tensor& T, int64_t i0, int cnt, bool skip, bool ema_on, double lr, double wd, double b1, double b2,
-                                            float bc1, float bc2_sqrt, double eps, float ema_w) {
+                                            float bc1, float bc2_sqrt, double eps, float ema_w, bool scaled, double gscale) {
     float g[4], w[4], m[4], v[4], e[4];
     if constexpr (VEC) {
         *reinterpret_cast<f32x4*>(w) = *reinterpret_cast<const f32x4*>(T.p + i0);
@@ -56,6 +62,7 @@ __device__ __forceinline__ void adamw_elems(const dm_adamw_tensor& T, int64_t i0
     for (int j = 0; j < 4; ++j) {
         if (j < cnt) {
             if (!skip) {
+                if (scaled) g[j] = (float)((double)g[j] / gscale);
                 if (wd != 0.0) w[j] = (float)((double)w[j] - lr * wd * (double)w[j]);
                 m[j] = (float)(b1 * (double)m[j] + (1.0 - b1) * (double)g[j]);
                 v[j] = (float)(b2 * (double)v[j] + (1.0 - b2) * (double)g[j] * (double)g[j]);
@@ -94,14 +101,16 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_ema_kernel(const dm_adamw_ar
     const float bc2 = (float)(1.0 - pow(p.beta2, t));
     const float bc2_sqrt = __builtin_sqrtf(bc2);
     const float ema_w = (float)(1.0 - p.ema_decay);
+    const bool scaled = p.grad_scale != nullptr;                // uniform: one read of the scale per workgroup
+    const double gscale = scaled ? (double)*p.grad_scale : 1.0;
     const bool vec = ((((uintptr_t)T.p | (uintptr_t)T.m | (uintptr_t)T.v | (uintptr_t)T.g | (uintptr_t)T.ema) & 15) == 0);
 #pragma unroll
     for (int k = 0; k < AW_VPT; ++k) {
         const int64_t i0 = base + ((int64_t)k * AW_THREADS + threadIdx.x) * 4;
         if (i0 >= T.n) break;
         const int cnt = (int)((T.n - i0) < 4 ? (T.n - i0) : 4);
-        if (vec && cnt == 4) adamw_elems<true>(T, i0, 4, skip, ema_on, p.lr, p.weight_decay, p.beta1, p.beta2, bc1, bc2_sqrt, p.eps, ema_w);
-        else adamw_elems<false>(T, i0, cnt, skip, ema_on, p.lr, p.weight_decay, p.beta1, p.beta2, bc1, bc2_sqrt, p.eps, ema_w);
+        if (vec && cnt == 4) adamw_elems<true>(T, i0, 4, skip, ema_on, p.lr, p.weight_decay, p.beta1, p.beta2, bc1, bc2_sqrt, p.eps, ema_w, scaled, gscale);
+        else adamw_elems<false>(T, i0, cnt, skip, ema_on, p.lr, p.weight_decay, p.beta1, p.beta2, bc1, bc2_sqrt, p.eps, ema_w, scaled, gscale);
     }
 }
 
@@ -127,6 +136,27 @@ __global__ __launch_bounds__(AW_THREADS) void grads_nonfinite_kernel(const dm_ad
         }
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) *p.nonfinite_out = 1.0f;
+}
+
+// one wave, one lane: four scalars of state.  The float * double products are evaluated in double and rounded once, as in torch's
+// amp_update_scale_cuda_kernel
+__global__ __launch_bounds__(64) void loss_scale_update_kernel(const dm_loss_scale_args p) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float found = *p.found_inf;
+    if (found != 0.0f) {
+        *p.scale = (float)((double)*p.scale * p.backoff_factor);
+        *p.growth_tracker = 0;
+    } else {
+        const int32_t successful = *p.growth_tracker + 1;
+        if (successful == p.growth_interval) {
+            const float grown = (float)((double)*p.scale * p.growth_factor);
+            if (__builtin_isfinite(grown)) *p.scale = grown;
+            *p.growth_tracker = 0;
+        } else {
+            *p.growth_tracker = successful;
+        }
+    }
+    if (p.skipped) *p.skipped += found;
 }
 
 }  // namespace dm
@@ -156,4 +186,17 @@ extern "C" int dm_adamw_ema_step(const dm_adamw_args* args, void* stream) {
     hipLaunchKernelGGL(adamw_steps_kernel, dim3((a.ntensors + 63) / 64), dim3(64), 0, st, a);
     hipLaunchKernelGGL(adamw_ema_kernel, dim3(a.nblocks), dim3(AW_THREADS), 0, st, a);
     return launch_status("dm_adamw_ema_step");
+}
+
+extern "C" int dm_loss_scale_update(const dm_loss_scale_args* args, void* stream) {
+    using namespace dm;
+    if (!args) { set_error("dm_loss_scale_update: null args"); return DM_ERR_ARG; }
+    const dm_loss_scale_args& a = *args;
+    if (!a.scale || !a.growth_tracker || !a.found_inf) { set_error("dm_loss_scale_update: null scale / growth_tracker / found_inf"); return DM_ERR_ARG; }
+    if (a.growth_interval < 1) { set_error("dm_loss_scale_update: growth_interval < 1"); return DM_ERR_ARG; }
+    if (!(a.growth_factor > 0.0 && __builtin_isfinite(a.growth_factor) && a.backoff_factor > 0.0 && __builtin_isfinite(a.backoff_factor))) {
+        set_error("dm_loss_scale_update: growth_factor and backoff_factor must be positive and finite"); return DM_ERR_ARG;
+    }
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+    return launch_status("dm_loss_scale_update");
 }

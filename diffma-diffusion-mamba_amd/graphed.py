@@ -209,17 +209,28 @@ class GraphedTrainStep:
     replay instead of hiding in a 55 ms host-bound step).  The caller keeps the ranks' weights identical at entry (train.py
     broadcasts them) and does NOT wrap the model in DistributedDataParallel.
 
+    fp16 (`loss_scale`: an optim.DeviceLossScale; the reference's own mode, train.py:95,247-263, is fp16 autocast under a GradScaler):
+    the scale lives in device memory and never visits the host.  It is the SEED of the backward (`loss.backward(gradient=scale)`:
+    no multiply launch, and the loss returned stays the unscaled one), the non-finite check runs on the scaled gradients, the fused
+    AdamW divides each gradient by the scale on its way into the moments, and GradScaler's grow / back-off rule is one more launch at
+    the end of the graph (`dm_loss_scale_update`, which also counts the skipped step).  In the two-graph form the scaled flat buffer is
+    all-reduced; `found` comes from it, identical on every rank, so every rank carries the same scale without a collective of its
+    own.  On a skipped step the EMA still moves towards the unchanged weights, as in the eager fp16 loop, where `update_ema` follows
+    a skipped `scaler.step`.  Construction leaves the scale and its growth tracker as it found them.  The staged form seeds its
+    groups differently and does not take a loss scale.
+
     step(z, t, y, y2, w) -> loss (a 0-d device tensor that is overwritten by the next replay; the local rank's loss).
     """
 
     def __init__(self, model, ema, optimizer, diffusion, z, t, y, y2, w, autocast_dtype=None, ema_decay=0.9999, warmup=3,
-                 process_group=None, split=None, stages=None):
+                 process_group=None, split=None, stages=None, loss_scale=None):
         assert z.is_cuda, "graph capture needs a ROCm device"
         for g in optimizer.param_groups:
             if not g.get("capturable", False):
                 raise ValueError("the optimizer must be built with capturable=True (and fused=True) to be captured")
         self.model, self.ema, self.opt, self.diffusion = model, ema, optimizer, diffusion
         self.amp, self.decay = autocast_dtype, ema_decay
+        self.ls = loss_scale
         self.sz, self.st = z.clone(), t.clone()
         self.sy, self.sy2, self.sw = y.clone(), y2.clone(), w.clone()
         self._mixers = [m for net in (model, ema) if net is not None for m in net.modules() if hasattr(m, "A_log")]
@@ -245,6 +256,8 @@ class GraphedTrainStep:
         import os
         if stages is None:
             stages = int(os.environ.get("DIFFMA_GRAPH_STAGES", "0"))
+        if stages and loss_scale is not None:
+            raise ValueError("the staged backward seeds its block groups itself and takes no loss_scale; use stages=0")
         self.staged = None
         if self.split and stages and hasattr(model, "blocks") and hasattr(model, "final_layer") and len(model.blocks) >= 2 * 4 \
                 and len(model.blocks) % 4 == 0 and type(model.blocks[0]).__name__ == "Spiral_MambaBlock":
@@ -272,6 +285,7 @@ class GraphedTrainStep:
         # below would zero the bias-correction count
         with torch.no_grad():
             o_snap = {id(v): v.detach().clone() for st in optimizer.state.values() for v in st.values() if torch.is_tensor(v)}
+            s_snap = (self.ls.scale.clone(), self.ls.growth_tracker.clone()) if self.ls is not None else None
         # Non-finite gradients (the reference's eager loop skips such a step, train.py:254-256): a replayed graph cannot branch on
         # the host, so the decision is taken ON THE DEVICE -- found_inf is computed from the (all-reduced, hence rank-identical)
         # gradients inside the graph and handed to the fused AdamW, which then leaves weights, moments and step count alone.
@@ -325,34 +339,55 @@ class GraphedTrainStep:
                 for v in st.values():
                     if torch.is_tensor(v):
                         v.copy_(o_snap[id(v)]) if id(v) in o_snap else v.zero_()
+            if s_snap is not None:      # ... and the warm-up's back-offs and growth are not the run's either
+                self.ls.scale.copy_(s_snap[0])
+                self.ls.growth_tracker.copy_(s_snap[1])
             self.skipped.zero_()        # the warm-up iterations ran on restored state: their dropped steps are not the run's
 
     def _step(self):
         with torch.autocast("cuda", dtype=self.amp, enabled=self.amp is not None):
             loss = self.diffusion.training_losses(self.model, self.sz, self.st, dict(y=self.sy, y2=self.sy2, w=self.sw))["loss"].mean()
-        loss.backward()
+        self._backward(loss)
         found = torch.zeros((), device=self.sz.device)            # 0-dim like GradScaler's (the fused AdamW subtracts it from its 0-dim step counters)
         grads = [p.grad for p in self._gp if p.grad is not None]
         if self._fused is not None and len(grads) == len(self._gp):
             self._fused.nonfinite(found)                                                    # one launch over the optimiser's tensor table
         elif grads:
-            torch._amp_foreach_non_finite_check_and_unscale_(grads, found, self._one)      # inv_scale 1: a pure check
+            # inv_scale 1: a pure check; with a loss scale its reciprocal, taken on the device as GradScaler takes it
+            torch._amp_foreach_non_finite_check_and_unscale_(grads, found, self._one if self.ls is None else self._inv_scale())
         self._guarded_update(found)
         self.opt.zero_grad(set_to_none=True)
         return loss.detach()
 
+    def _backward(self, loss):
+        if self.ls is None:
+            loss.backward()
+        else:
+            loss.backward(gradient=self.ls.scale)                     # the scale rides in as the seed: d(scale * loss) without a launch
+
+    def _inv_scale(self):
+        return self.ls.scale.double().reciprocal().float()
+
     def _guarded_update(self, found):
         if self._fused is not None and all(p.grad is not None for p in self._gp):
-            self._fused.step(found)                                   # weights, moments, counters and the EMA in one pass; found = 1 -> EMA only
+            # weights, moments, counters and the EMA in one pass; found = 1 -> EMA only.  With a loss scale every gradient is divided by
+            # it on its way in, and the scale's update (back off / grow) counts the skipped step in its own launch
+            self._fused.step(found, grad_scale=self.ls.scale if self.ls is not None else None)
             with torch.no_grad():
-                self.skipped += found
+                if self.ls is not None:
+                    self.ls.update(found, skipped=self.skipped)
+                else:
+                    self.skipped += found
                 if self._ep_rest:
                     torch._foreach_lerp_(self._ep_rest, self._mp_rest, 1.0 - self.decay)
             return
         self.opt.grad_scale, self.opt.found_inf = None, found          # read by the fused AdamW: found_inf = 1 -> no update
         self.opt.step()
         with torch.no_grad():
-            self.skipped += found
+            if self.ls is not None:
+                self.ls.update(found, skipped=self.skipped)
+            else:
+                self.skipped += found
             if self.ema is not None:
                 # ONE multi-tensor pass (ema += (1 - decay) (model - ema): 3 accesses per element; mul_ + add_ are 5, and a blend
                 # gated by `found` on the device needs 8 -- at one sample per GPU the EMA and AdamW passes over the 89 M parameters
@@ -364,7 +399,7 @@ class GraphedTrainStep:
     def _fwd_bwd(self):
         with torch.autocast("cuda", dtype=self.amp, enabled=self.amp is not None):
             loss = self.diffusion.training_losses(self.model, self.sz, self.st, dict(y=self.sy, y2=self.sy2, w=self.sw))["loss"].mean()
-        loss.backward()
+        self._backward(loss)
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in self._gp]
         self.flat = torch.cat([g.reshape(-1).float() for g in grads])          # one buffer = one collective
         return loss.detach()
@@ -423,6 +458,9 @@ class GraphedTrainStep:
                 found = bad if found is None else torch.maximum(found, bad)
             if dst:
                 torch._foreach_copy_(dst, src)              # ONE multi-tensor launch (per-parameter copy_ was 459 launches per step)
+            if self.ls is not None and self._fused is None:
+                # torch's AdamW reads unscaled gradients: the one-graph form's unscale (found is already set from the flat buffer)
+                torch._amp_foreach_non_finite_check_and_unscale_([p.grad for p in self._gp], found, self._inv_scale())
         self._guarded_update(found)
 
     def step(self, z, t, y, y2, w):

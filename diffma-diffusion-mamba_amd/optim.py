@@ -10,12 +10,13 @@ reference's own configuration -- the optimiser and the EMA are a sixth of the tr
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
 
 from . import _lib
-from ._lib import dm_adamw_args
+from ._lib import dm_adamw_args, dm_loss_scale_args
 
 ENABLED = os.environ.get("DIFFMA_FUSED_OPT", "1") == "1"          # 0: torch's fused AdamW + _foreach_lerp_ again (A/B runs)
 
@@ -37,8 +38,9 @@ def supported(optimizer, params, ema_params=None) -> bool:
 
 
 class FusedAdamWEMA:
-    """step(found_inf=None): one AdamW step of `optimizer` on `params` (the tensors with a gradient) and, with `ema_params`, the EMA
-    step towards the new weights, in one pass.  The tensor table is rebuilt when a pointer moved (eager training re-allocates the
+    """step(found_inf=None, grad_scale=None): one AdamW step of `optimizer` on `params` (the tensors with a gradient) and, with
+    `ema_params`, the EMA step towards the new weights, in one pass.  grad_scale (0-dim fp32 device tensor): the gradients are that
+    many times the true ones (a loss scale); they are divided by it inside the pass and left scaled in memory.  The tensor table is rebuilt when a pointer moved (eager training re-allocates the
     gradients every step; inside a captured graph everything is static and the table is built once, at capture)."""
 
     def __init__(self, optimizer, params, ema_params=None, ema_decay=0.9999, ema_on_skip=True):
@@ -118,7 +120,7 @@ class FusedAdamWEMA:
         return found
 
     @torch.no_grad()
-    def step(self, found_inf=None):
+    def step(self, found_inf=None, grad_scale=None):
         live = self._live()
         if not live:
             return
@@ -131,7 +133,61 @@ class FusedAdamWEMA:
         a.ema_decay = self.decay
         a.found_inf = found_inf.data_ptr() if found_inf is not None else 0
         a.ema_on_skip = 1 if self.ema_on_skip else 0
+        a.grad_scale = grad_scale.data_ptr() if grad_scale is not None else 0
         dev = self.params[0].device
         with torch.cuda.device(dev):
             _lib.call("dm_adamw_ema_step", a, torch.cuda.current_stream(dev).cuda_stream)
-        self._keep = (a, found_inf)
+        self._keep = (a, found_inf, grad_scale)
+
+
+SCALE_STATE_KEYS = ("scale", "growth_factor", "backoff_factor", "growth_interval", "_growth_tracker")
+
+
+def scale_state_dict(scale, growth_factor, backoff_factor, growth_interval, growth_tracker):
+    """`torch.amp.GradScaler.state_dict()`'s public format from plain numbers."""
+    return dict(zip(SCALE_STATE_KEYS, (float(scale), float(growth_factor), float(backoff_factor), int(growth_interval), int(growth_tracker))))
+
+
+def scale_state_parse(sd):
+    """The five numbers of a GradScaler-format state dict, in SCALE_STATE_KEYS' order; an empty dict (a disabled GradScaler's) and a
+    missing key are errors."""
+    missing = [k for k in SCALE_STATE_KEYS if k not in sd]
+    if missing:
+        raise KeyError(f"not a GradScaler state dict: missing {missing}")
+    return float(sd["scale"]), float(sd["growth_factor"]), float(sd["backoff_factor"]), int(sd["growth_interval"]), int(sd["_growth_tracker"])
+
+
+class DeviceLossScale:
+    """The loss scale of fp16 training kept, applied and updated ON THE DEVICE, so that a replayed hipGraph can carry it
+    (reference train.py:95,247-263 trains under a `torch.amp.GradScaler`, whose skip decision and scale update go through the host).
+    `scale` (0-dim fp32) seeds the backward and is handed to FusedAdamWEMA.step(grad_scale=); `update(found_inf)` is GradScaler's
+    grow / back-off rule as one launch (`dm_loss_scale_update`).  The defaults are GradScaler's, and so is the state-dict format."""
+
+    def __init__(self, device, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        if not (growth_factor > 0.0 and math.isfinite(growth_factor) and backoff_factor > 0.0 and math.isfinite(backoff_factor)):
+            raise ValueError("growth_factor and backoff_factor must be positive and finite")
+        if int(growth_interval) < 1:
+            raise ValueError("growth_interval must be at least 1")
+        self.device = torch.device(device)
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        self.scale = torch.full((), float(init_scale), dtype=torch.float32, device=self.device)
+        self.growth_tracker = torch.zeros((), dtype=torch.int32, device=self.device)
+
+    @torch.no_grad()
+    def update(self, found_inf, skipped=None):
+        """found_inf (0-dim fp32 device tensor): back off or count a clean step and grow; skipped (optional, same kind) += found_inf."""
+        a = dm_loss_scale_args()
+        a.scale, a.growth_tracker, a.found_inf = self.scale.data_ptr(), self.growth_tracker.data_ptr(), found_inf.data_ptr()
+        a.skipped = skipped.data_ptr() if skipped is not None else 0
+        a.growth_factor, a.backoff_factor, a.growth_interval = self.growth_factor, self.backoff_factor, self.growth_interval
+        with torch.cuda.device(self.device):
+            _lib.call("dm_loss_scale_update", a, torch.cuda.current_stream(self.device).cuda_stream)
+        self._keep = (a, found_inf, skipped)
+
+    def state_dict(self):
+        return scale_state_dict(self.scale.item(), self.growth_factor, self.backoff_factor, self.growth_interval, self.growth_tracker.item())
+
+    def load_state_dict(self, sd):
+        scale, self.growth_factor, self.backoff_factor, self.growth_interval, tracker = scale_state_parse(sd)
+        self.scale.fill_(scale)
+        self.growth_tracker.fill_(tracker)

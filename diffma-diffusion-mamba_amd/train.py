@@ -7,7 +7,8 @@ Same YAML keys, same step (t ~ U{0..T-1}, training_losses, AdamW lr 1e-4 wd 0, E
 dict {"model","ema","opt","args"} at results_dir/<idx>-<model>/checkpoints/<step:07d>.pt, same log line.
 Differences, all deliberate (SURVEY.md A.4-5,10):
   * --autocast means bf16 (no GradScaler needed) by default; `--amp-dtype fp16` gives the reference's own mode, fp16
-    autocast with a GradScaler (train.py:95,247-263), on the same kernels (fp16 I/O, fp32 scan state).
+    autocast with a GradScaler (train.py:95,247-263), on the same kernels (fp16 I/O, fp32 scan state).  With `--graph-train true`
+    the fp16 step is replayed from a hipGraph and the loss scale is kept, applied and updated on the device (optim.DeviceLossScale).
   * a non-finite loss is detected COLLECTIVELY (all-reduce of a flag) and the step is skipped on every rank;
     the reference `continue`s on one rank only, which dead-locks DDP.
   * frozen encoders (SD-VAE, BiomedCLIP) need network weights: the real-data path runs through the seam of data.py (NpyDataset +
@@ -91,8 +92,9 @@ GRAPH_AUTO_MAX_BATCH = 32      # `graph_train: auto`: per-GPU batches up to this
 def graph_train_decision(setting, device_type, accumulation_steps, local_batch, fp16):
     """graph_train = true / false / "auto".  The reference's own configuration (config/brain.yaml: global batch 8 on 8 GPUs) runs ONE
     sample per GPU, where an eager step is bound by the host's launch rate (~50 ms) and the replayed step takes 6.5 ms: "auto" turns the
-    graphed step on for per-GPU batches up to GRAPH_AUTO_MAX_BATCH when nothing rules it out (a ROCm device, no gradient accumulation,
-    not fp16 -- the GradScaler's skip decision is a host branch); "true" insists (and train() raises for fp16)."""
+    graphed step on for per-GPU batches up to GRAPH_AUTO_MAX_BATCH when nothing rules it out (a ROCm device, no gradient accumulation)
+    and the run is not fp16: that mode is opt-in.  "true" insists, fp16 included: the graphed fp16 step keeps its loss scale on the
+    device (optim.DeviceLossScale) where the eager loop keeps a GradScaler."""
     if isinstance(setting, str):
         v = setting.strip().lower()
         if v == "auto":
@@ -218,12 +220,17 @@ def main(args):
     ddp.train()
     ema.eval()
     log_steps, running_loss, start_time = 0, 0.0, time()
+    scale_note = ""                      # fp16 graphed step: the current loss scale, read at the log line's host sync
     skipped_seen = 0                     # graphed steps dropped on the device that the step counter has already been corrected for
     max_steps = args.get("max_steps", None)
     amp = (torch.float16 if args.get("amp_dtype", "bf16") == "fp16" else torch.bfloat16) if args.autocast else None
     scaler = torch.amp.GradScaler(device.type, enabled=amp == torch.float16)     # no-op unless fp16 (reference train.py:95)
+    loss_scale = None
     if amp == torch.float16 and use_graph:
-        raise NotImplementedError("--graph-train with fp16: the GradScaler's skip decision is a host branch; use bf16")
+        # the graphed step's GradScaler: same defaults, but scale, skip decision and update stay on the device.  Like the eager
+        # loop's scaler it is not checkpointed: the scale restarts at its initial value on resume
+        from .optim import DeviceLossScale
+        loss_scale = DeviceLossScale(device)
     logger.info(f"Training for {args.epochs} epochs...")
     for epoch in range(args.epochs):
         logger.info(f"Beginning epoch {epoch}...")
@@ -232,19 +239,22 @@ def main(args):
             if use_graph:
                 if graphed is None:
                     from .graphed import GraphedTrainStep
-                    graphed = GraphedTrainStep(model, ema, opt, diffusion, z, t, y, y2, w, autocast_dtype=amp, ema_decay=0.999,
+                    graphed = GraphedTrainStep(model, ema, opt, diffusion, z, t, y, y2, w, autocast_dtype=amp, ema_decay=0.999, loss_scale=loss_scale,
                                                split=True if os.environ.get("DIFFMA_GRAPH_SPLIT") == "1" else None)
                 loss = graphed.step(z, t, y, y2, w)             # forward, backward, AdamW and EMA in one replay
                 train_steps += 1
                 log_steps += 1
                 if train_steps % args.log_every == 0:           # the only host sync of the graphed loop
                     # non-finite steps were dropped ON THE DEVICE (found_inf from the all-reduced gradients, the same decision on
-                    # every rank: graphed.GraphedTrainStep._guarded_update); the host only reports them
+                    # every rank: graphed.GraphedTrainStep._guarded_update); the host only reports them.  With fp16 they are the loss
+                    # scale's overflows as well as NaN inputs: one count, one correction
                     lv, nskip = loss.item(), int(graphed.skipped.item())
                     if nskip > skipped_seen:                    # dropped steps do not count as optimisation steps (reference `continue`)
                         logger.info(f"nan......      ignore losses......   ({nskip} graphed steps skipped so far)")
                         train_steps -= nskip - skipped_seen
                         skipped_seen = nskip
+                    if loss_scale is not None:
+                        scale_note = f", Loss Scale: {loss_scale.scale.item():g}"
                     running_loss = (lv if math.isfinite(lv) else 0.0) * log_steps   # the log line shows the latest loss instead of a running mean
             else:
                 with torch.autocast(device.type, dtype=amp, enabled=amp is not None):
@@ -285,7 +295,7 @@ def main(args):
                 avg = torch.tensor(running_loss / max(log_steps, 1), device=device)
                 dist.all_reduce(avg, op=dist.ReduceOp.SUM)
                 pct = local_batch * item / data.n * 100
-                logger.info(f"({pct:.1f}%) (step={train_steps:07d}) Train Loss: {avg.item() / world:.4f}, Train Steps/Sec: {steps_per_sec:.2f}")
+                logger.info(f"({pct:.1f}%) (step={train_steps:07d}) Train Loss: {avg.item() / world:.4f}, Train Steps/Sec: {steps_per_sec:.2f}{scale_note}")
                 running_loss, log_steps, start_time = 0.0, 0, time()
             if train_steps % args.ckpt_every == 0 and train_steps > 0:
                 if rank == 0:
@@ -307,7 +317,7 @@ def cli(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--wandb", action="store_true", help="accepted for compatibility; wandb is not installed offline")
     p.add_argument("--autocast", action="store_true", help="autocast (bf16 unless --amp-dtype fp16)")
-    p.add_argument("--amp-dtype", default="bf16", choices=["bf16", "fp16"], help="fp16 = the reference's mode: fp16 autocast + GradScaler")
+    p.add_argument("--amp-dtype", default="bf16", choices=["bf16", "fp16"], help="fp16 = the reference's mode: fp16 autocast + GradScaler (graphed: a loss scale kept on the device)")
     p.add_argument("--use-mamba2", action="store_true")
     p.add_argument("--synthetic", action="store_true", help="synthetic latents/conditioning instead of datasets + frozen encoders")
     p.add_argument("--max-steps", type=int, default=None)
@@ -315,7 +325,8 @@ def cli(argv=None):
                    help="all-reduce 16-bit copies of the DDP gradient buckets (opt-in; default none = fp32 like the reference)")
     p.add_argument("--graph-train", nargs="?", const="true", default=None, choices=["true", "false", "auto"],
                    help="replay the whole optimisation step from a hipGraph (for small batches; with several ranks: two graphs around one "
-                        "gradient all-reduce); `auto`: on for per-GPU batches up to 32.  Also the YAML key graph_train")
+                        "gradient all-reduce); `auto`: on for per-GPU batches up to 32, except with fp16, which only `true` graphs (loss scale kept and "
+                        "updated on the device).  Also the YAML key graph_train")
     p.add_argument("--config", type=str, required=True)
     a = p.parse_args(argv)
     over = {k: v for k, v in vars(a).items() if v is not None and k != "config"}

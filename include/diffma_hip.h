@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DM_ABI_VERSION 36
+#define DM_ABI_VERSION 37
 
 typedef enum {
     DM_OK = 0,
@@ -127,6 +127,20 @@ int dm_training_loss_bwd(const dm_training_loss_args *args, void *stream);
  * caller lists every chunk of every tensor once (two int32 device arrays of nblocks entries).  found_inf (device scalar or NULL):
  * a non-zero value leaves p, m, v and the counters untouched; the EMA then still takes its step towards the unchanged weights if
  * ema_on_skip != 0 and is left alone otherwise.  Two launches on `stream` (counters, then elements); graph-capturable.
+ *
+ * Loss scaling on the device (ABI 37), for the fp16 training step replayed from a hipGraph (reference train.py:95,247-263: fp16
+ * autocast under a GradScaler).  grad_scale (device scalar or NULL, the LAST field: a zero-initialised struct behaves as before):
+ * every gradient element is divided by *grad_scale before it enters the moments -- the `grad_scale` branch of torch's fused AdamW,
+ * the quotient evaluated in double and rounded once to fp32.  The unscaled gradient is NOT written back (the pass stays at 36 bytes
+ * per element; the graphed step drops the gradients after the update).  found_inf keeps its meaning with a scale present;
+ * dm_grads_nonfinite runs on the scaled gradients.
+ * dm_loss_scale_update is the arithmetic of torch._amp_update_scale_ as one launch of one wave:
+ *      found_inf != 0:  scale = (float)(scale * backoff_factor), growth_tracker = 0
+ *      otherwise:       growth_tracker += 1;  on reaching growth_interval: growth_tracker = 0 and scale = (float)(scale * growth_factor)
+ *                       if that product is finite (an infinite one leaves the scale alone)
+ *      skipped != NULL: *skipped += *found_inf     (the graphed step's count of dropped steps, in the same launch)
+ * DM_ERR_ARG and nothing written for a NULL scale / growth_tracker / found_inf, growth_interval < 1, or a factor that is not positive
+ * and finite.  Graph-capturable.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     float *p, *m, *v;
@@ -144,13 +158,24 @@ typedef struct {
     const float *found_inf;
     int32_t ema_on_skip, _pad;
     float *nonfinite_out;      /* dm_grads_nonfinite only */
+    const float *grad_scale;   /* ABI 37: NULL = the gradients are taken as they are */
 } dm_adamw_args;
+
+typedef struct {
+    float *scale;
+    int32_t *growth_tracker;
+    const float *found_inf;
+    float *skipped;            /* may be NULL */
+    double growth_factor, backoff_factor;
+    int32_t growth_interval;
+} dm_loss_scale_args;
 
 int dm_adamw_chunk(void);
 int dm_adamw_ema_step(const dm_adamw_args *args, void *stream);
 /* *nonfinite_out = 1 if any element of any gradient in the table is Inf / NaN (the caller zeroes it first; nothing else of `args` but the
  * table and the block arrays is read): the device-side decision of the reference's `if not torch.isfinite(...)`: continue (train.py:254-256). */
 int dm_grads_nonfinite(const dm_adamw_args *args, void *stream);
+int dm_loss_scale_update(const dm_loss_scale_args *args, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Selective scan, forward.   Replaces selective_scan_cuda.fwd behind
