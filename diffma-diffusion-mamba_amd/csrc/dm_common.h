@@ -160,6 +160,10 @@ __device__ __forceinline__ rsrc_t make_rsrc_2g(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), /*stride*/ 0, /*num_records*/ (int)0x80000000u, 0x00020000);
 }
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4_t ld16(const rsrc_t& r, int byte_off) {     // one 16-byte piece of a row
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
+    return (u32x4_t){v[0], v[1], v[2], v[3]};
+}
 // W 32-bit words of a lane (W % 4 == 0) as 16-byte buffer accesses, group g of 4 words at byte offset g * gstride: with
 // gstride = 16 * (lanes in a row) every instruction reads / writes one dense run of 16-byte pieces.  (The lane-contiguous form,
 // 32 bytes per lane written by two instructions at a 32-byte lane stride, halves the instruction count as well but leaves every

@@ -16,14 +16,12 @@
 // per-head dt is read in the kernel (token order, through the gather table), no [nseq, L, Din] delta tensor exists.
 // 16-bit I/O only (the score tile is rounded to the I/O dtype); fp32 I/O stays on the A-shared scan.  Backward twin: ssd_bwd.hip.
 #include <type_traits>
-#include "dm_mfma.h"
+#include "ssd_fwd_common.h"
 
 namespace dm {
 
-constexpr int SSD_TILE = 32;
 constexpr int SSD_MAXT = 7;                       // L <= 224
 constexpr int SSD_MAXL = SSD_TILE * SSD_MAXT;
-constexpr int SSD_PITCH = 20;                     // dwords per staged tile row (32 channels = 16 dwords, +4 pad)
 
 // One wave64 per (sequence, head, 32-column half of the head): 56 VGPRs of X fragments, ~150 registers, 3 waves per SIMD.
 //
@@ -40,8 +38,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
     __shared__ __attribute__((aligned(16))) float s2_lds[2][SSD_MAXL + 32];    // log2-domain log-decay (prefix sums, ping-pong)
     __shared__ __attribute__((aligned(16))) float dt_lds[SSD_MAXL];
     __shared__ int zi_lds[SSD_MAXL], oi_lds[SSD_MAXL];
-    // 32-row x 32-channel staging tiles (row pitch 80 B: the two key halves of a fragment read land on disjoint banks): global
-    // traffic is whole 16-byte pieces of a row, the (key, channel) element order of the fragments is produced by LDS reads
+    // 32-row x 32-channel staging tiles (ssd_fwd_common.h): the gate tile goes in through one, the output tile out through the other
     __shared__ __attribute__((aligned(16))) uint32_t tile_a[SSD_TILE * SSD_PITCH], tile_b[SSD_TILE * SSD_PITCH];
 
     const int lane = threadIdx.x;
@@ -72,14 +69,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
         const int i = SSD_TILE * it + trow;
         const int ic = i < L ? i : L - 1;                                 // rows past the end: clamped here, zeroed below
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_x, ic * sl_x + cb + 16 * q, 0, 0);
-            xq[it][q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-        }
+        for (int q = 0; q < 2; ++q) xq[it][q] = ld16(r_x, ic * sl_x + cb + 16 * q);
         const int j = SSD_TILE * it + col;
         const int jc = j < L ? j : L - 1;
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_B, jc * sl_B + kh * 8 * ES, 0, 0);
-        bq[it] = (u32x4_t){v[0], v[1], v[2], v[3]};
+        bq[it] = ld16(r_B, jc * sl_B + kh * 8 * ES);
     }
 
     // ---- per-position scalars: dt = softplus(raw + bias), log-decay prefix sums, row tables -------------------------------
@@ -126,41 +119,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 #pragma unroll
         for (int w = 0; w < 4; ++w) bfrag[it][w] = O::pack(O::lo(bq[it][w]) * sc, O::hi(bq[it][w]) * sc);
     }
-    // X as B-fragments of the output product, keys in accumulator order: slot e of (it, ks) is key 32it + 4kh + 8(2ks + e/4) + e%4
-    u32x4_t xfrag[SSD_MAXT][2];
-    {
-        const uint16_t* const ta16 = reinterpret_cast<const uint16_t*>(tile_a);
-#pragma unroll
-        for (int it = 0; it < SSD_MAXT; ++it) {
-            const bool live = SSD_TILE * it + trow < L;
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                *reinterpret_cast<u32x4_t*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = live ? xq[it][q] : (u32x4_t){0u, 0u, 0u, 0u};
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                uint32_t w4[4];
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    const int k0 = 4 * kh + 8 * (2 * ks + (e2 >> 1)) + 2 * (e2 & 1);
-                    const uint32_t lo = ta16[k0 * (2 * SSD_PITCH) + col], hi = ta16[(k0 + 1) * (2 * SSD_PITCH) + col];
-                    w4[e2] = lo | (hi << 16);
-                }
-                xfrag[it][ks] = (u32x4_t){w4[0], w4[1], w4[2], w4[3]};
-            }
-            __syncthreads();
-        }
-    }
+    u32x4_t xfrag[SSD_MAXT][2];                                          // X as B-fragments of the output product, keys in accumulator order
+    sf_x_frags(xfrag, xq, tile_a, L, lane);
 
     // C rows (the B-operand of the score product: lane (col l, kh) holds C[l][8kh .. +7]) and the unscaled B rows of the diagonal
     // tile are fetched one query tile ahead
     auto load_cb = [&](int t, u32x4_t& c, u32x4_t& b) {
         const int j = SSD_TILE * t + col;
         const int jc = j < L ? j : L - 1;
-        const auto vc = __builtin_amdgcn_raw_buffer_load_b128(r_C, jc * sl_C + kh * 8 * ES, 0, 0);
-        const auto vb = __builtin_amdgcn_raw_buffer_load_b128(r_B, jc * sl_B + kh * 8 * ES, 0, 0);
-        c = (u32x4_t){vc[0], vc[1], vc[2], vc[3]};
-        b = (u32x4_t){vb[0], vb[1], vb[2], vb[3]};
+        c = ld16(r_C, jc * sl_C + kh * 8 * ES);
+        b = ld16(r_B, jc * sl_B + kh * 8 * ES);
     };
     u32x4_t cnext, bnext;
     load_cb(0, cnext, bnext);
@@ -176,14 +144,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
         u32x4_t zq[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};                // the gate tile of this query tile, in flight under the products
         const int lrow = SSD_TILE * lt + trow;
         const int lrc = lrow < L ? lrow : L - 1;
-        if (p.z) {
-            const int zr = zi_lds[lrc];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zr * sl_z + cb + 16 * q, 0, 0);
-                zq[q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-            }
-        }
+        if (p.z) sf_gate_issue(zq, r_z, zi_lds[lrc] * sl_z + cb, true);   // (dm_ssd_fwd takes 16-byte gate rows only at d_state 16)
         const float alpha = fast_exp2(s2l - mlt);
         u32x4_t cfrag;
 #pragma unroll
@@ -206,11 +167,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
                     const f32x2 gs = (f32x2){g[2 * r2], g[2 * r2 + 1]} * (f32x2){delta, delta};        // v_pk_mul_f32
                     wp[r2] = O::pack(gs.x, gs.y);
                 }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                    yacc = O::m32(wf, xfrag[it][ks], yacc);
-                }
+                sf_times_x<O>(yacc, wp, xfrag[it]);
             }
         }
         // ---- the diagonal tile: element-wise decay and causal mask on unscaled operands ----
@@ -225,66 +182,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void ss
 #pragma unroll
             for (int r = 0; r < 16; ++r) g[r] = 0.0f;
             g = O::m32(bd, craw, g);
-            uint32_t wp[8];
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 si = *reinterpret_cast<const f32x4*>(&s2[SSD_TILE * lt + 4 * kh + 8 * r4]);
-                float wv[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int ik = SSD_TILE * lt + 4 * kh + 8 * r4 + r;
-                    wv[r] = (ik <= lq) ? g[4 * r4 + r] * fast_exp2(s2l - si[r]) : 0.0f;
-                }
-                wp[2 * r4] = O::pack(wv[0], wv[1]);
-                wp[2 * r4 + 1] = O::pack(wv[2], wv[3]);
-            }
-#pragma unroll
-            for (int it = 0; it < SSD_MAXT; ++it) {                       // (compile-time index into xfrag)
-                if (it == lt) {
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                        yacc = O::m32(wf, xfrag[it][ks], yacc);
-                    }
-                }
-            }
+            sf_diag<O, false>(yacc, g, &s2[SSD_TILE * lt + 4 * kh], nullptr, SSD_TILE * lt + 4 * kh, lq, s2l, xfrag[lt]);
         }
-        // ---- epilogue of the query tile: + D x, gate, scatter.  yacc[4 r4 + r] = Y[32lt + 4kh + 8 r4 + r][this lane's channel] ----
-        if (p.z) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4_t*>(&tile_a[trow * SSD_PITCH + thf * 8 + 4 * q]) = zq[q];
-        }
-        __syncthreads();
-        {
-            const uint16_t* const ta16 = reinterpret_cast<const uint16_t*>(tile_a);
-            uint16_t* const tb16 = reinterpret_cast<uint16_t*>(tile_b);
-#pragma unroll
-            for (int it = 0; it < SSD_MAXT; ++it) {                       // (compile-time index into xfrag)
-                if (it == lt) {
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 4 * kh + 8 * r4 + r;
-                            const int e = 4 * (r4 & 1) + r;
-                            const uint32_t xw = xfrag[it][r4 >> 1][e >> 1];
-                            const float xv = (e & 1) ? O::hi(xw) : O::lo(xw);
-                            float y = yacc[4 * r4 + r] + Dh * xv;
-                            if (p.z) y *= silu_f(O::lo((uint32_t)ta16[row * (2 * SSD_PITCH) + col]));
-                            tb16[row * (2 * SSD_PITCH) + col] = (uint16_t)(O::pack(y, 0.0f) & 0xffffu);
-                        }
-                }
-            }
-        }
-        __syncthreads();
-        if (lrow < L) {
-            const int orow = oi_lds[lrow];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&tile_b[trow * SSD_PITCH + thf * 8 + 4 * q]);
-                __builtin_amdgcn_raw_buffer_store_b128(v, r_o, orow * sl_o + cb + 16 * q, 0, 0);
-            }
-        }
+        // ---- epilogue of the query tile: + D x, gate (in through tile_a), scatter (out through tile_b) ----
+        sf_epilogue<O, false>(yacc, xfrag[lt], Dh, p.z != nullptr, zq, tile_a, tile_b, r_o, sl_o, cb, &oi_lds[lrc], lrow < L, lane);
     }
 }
 
@@ -315,8 +216,7 @@ constexpr int SSDW_TABS = 0;                                 // byte offsets: pe
 constexpr int SSDW_IDX = SSDW_TABS + SSDW_HEADS * 3 * SSDW_TAB * 4;                 // z rows | out rows
 constexpr int SSDW_TILES = SSDW_IDX + 2 * SSDW_TAB * 4;                              // one 32 x 32 staging tile per wave
 constexpr int SSDW_BC = SSDW_TILES + SSDW_WAVES * SSD_TILE * SSD_PITCH * 4;          // B rows, then C rows
-constexpr int ssdw_pitch(int nk) { return 32 * nk + 16; }                           // bytes per staged B / C row
-constexpr int ssdw_lds_bytes(int nk, int rows) { return SSDW_BC + 2 * rows * ssdw_pitch(nk); }
+constexpr int ssdw_lds_bytes(int nk, int rows) { return SSDW_BC + 2 * rows * ssd_bc_pitch(nk); }
 static_assert(SSDW_TAB >= SSD_MAXL && SSDW_TAB % WAVE == 0 && SSDW_TAB == 256, "eight doubling steps leave the prefix sums in the ping table");
 static_assert(ssdw_lds_bytes(8, SSD_MAXL) <= 160 * 1024, "LDS of a CU");
 
@@ -324,8 +224,7 @@ template <typename T, int NK>
 __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void ssd_fwd_wide_kernel(const dm_ssd_fwd_args p) {
     using O = mfma<T>;
     constexpr int ES = (int)sizeof(T);
-    constexpr int PITCH = ssdw_pitch(NK);
-    constexpr int PPR = 2 * NK;                                          // 16-byte pieces of a B / C row
+    constexpr int PITCH = ssd_bc_pitch(NK);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
 
     const int tid = threadIdx.x;
@@ -362,45 +261,8 @@ __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     // ---- X of this wave's (head, half) goes out first, then the workgroup's share of the B / C rows ---------------------------
     const int cb = ((head_live ? h : 0) * 64 + half * 32 + thf * 16) * ES;   // byte offset of this lane's 16 staged channels in a row
     u32x4_t xq[SSD_MAXT][2];
-    if (head_live) {
-#pragma unroll
-        for (int it = 0; it < SSD_MAXT; ++it) {
-            const int i = SSD_TILE * it + trow;
-            const int ic = i < L ? i : L - 1;                             // rows past the end: clamped here, zeroed below
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_x, ic * sl_x + cb + 16 * q, 0, 0);
-                xq[it][q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-            }
-        }
-    }
-    {
-        const int npieces = rows * PPR;                                  // rows past the end are staged as copies of the last row
-        for (int q0 = 0; q0 < npieces; q0 += 4 * SSDW_THREADS) {
-            u32x4_t vb[4], vc[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int q = q0 + u * SSDW_THREADS + tid;
-                if (q < npieces) {
-                    const int r = q / PPR, pc = q - r * PPR;
-                    const int rc = r < L ? r : L - 1;
-                    const auto b = __builtin_amdgcn_raw_buffer_load_b128(r_B, rc * sl_B + 16 * pc, 0, 0);
-                    const auto c = __builtin_amdgcn_raw_buffer_load_b128(r_C, rc * sl_C + 16 * pc, 0, 0);
-                    vb[u] = (u32x4_t){b[0], b[1], b[2], b[3]};
-                    vc[u] = (u32x4_t){c[0], c[1], c[2], c[3]};
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int q = q0 + u * SSDW_THREADS + tid;
-                if (q < npieces) {
-                    const int r = q / PPR, pc = q - r * PPR;
-                    *reinterpret_cast<u32x4_t*>(Bl + r * PITCH + 16 * pc) = vb[u];
-                    *reinterpret_cast<u32x4_t*>(Cl + r * PITCH + 16 * pc) = vc[u];
-                }
-            }
-        }
-    }
+    if (head_live) sf_x_issue(xq, r_x, sl_x, cb, 0, L, lane);
+    sf_stage_bc<NK, 4>(Bl, Cl, r_B, r_C, sl_B, sl_C, 0, L, rows, tid, SSDW_THREADS);
 
     // ---- per-position scalars of a head by its first wave: dt = softplus(raw + bias), log-decay; row tables by wave 0 ---------
     float Ah = 0.0f, Dh = 0.0f;
@@ -461,35 +323,10 @@ __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     __syncthreads();
     auto m_of = [&](int t) -> float { return t == 0 ? 0.0f : s2[SSD_TILE * t - 1]; };   // log-decay just before tile t
 
-    // ---- X as B-fragments of the output product, keys in accumulator order: slot e of (it, ks) is key 32it + 4kh + 8(2ks + e/4) + e%4
-    u32x4_t xfrag[SSD_MAXT][2];
-    {
-        const uint16_t* const t16 = reinterpret_cast<const uint16_t*>(tile);
-#pragma unroll
-        for (int it = 0; it < SSD_MAXT; ++it) {
-            const bool row_live = SSD_TILE * it + trow < L;
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                *reinterpret_cast<u32x4_t*>(&tile[trow * SSD_PITCH + thf * 8 + 4 * q]) = row_live ? xq[it][q] : (u32x4_t){0u, 0u, 0u, 0u};
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                uint32_t w4[4];
-#pragma unroll
-                for (int e2 = 0; e2 < 4; ++e2) {
-                    const int k0 = 4 * kh + 8 * (2 * ks + (e2 >> 1)) + 2 * (e2 & 1);
-                    const uint32_t lo = t16[k0 * (2 * SSD_PITCH) + col], hi = t16[(k0 + 1) * (2 * SSD_PITCH) + col];
-                    w4[e2] = lo | (hi << 16);
-                }
-                xfrag[it][ks] = (u32x4_t){w4[0], w4[1], w4[2], w4[3]};
-            }
-            __syncthreads();
-        }
-    }
+    u32x4_t xfrag[SSD_MAXT][2];                                          // X as B-fragments of the output product, keys in accumulator order
+    sf_x_frags(xfrag, xq, tile, L, lane);
 
-    // the gate is a view of the in_proj output, whose rows are 2 Din + 2 N + H elements: a multiple of 8 with the factory models' 16 or
-    // 24 heads, not with the two heads of a d_model 64 mixer
-    const bool z_rows16 = (((uintptr_t)p.z & 15) | (uintptr_t)(p.z_ss & 7) | (uintptr_t)(p.z_sl & 7)) == 0;
+    const bool z_rows16 = sf_gate_rows16(p.z, p.z_ss, p.z_sl);
     // fragments of the score product G^T = B_it C_lt^T: lane (row = col, kh) holds states 16k + 8kh .. +7 of slice k
     const uint8_t* const bl = Bl + col * PITCH + 16 * kh;
     const uint8_t* const cl = Cl + col * PITCH + 16 * kh;
@@ -502,21 +339,7 @@ __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         u32x4_t zq[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};                // the gate tile of this query tile, in flight under the products
         const int lrow = SSD_TILE * lt + trow;
         const int lrc = lrow < L ? lrow : L - 1;
-        if (p.z) {
-            const int zr = zi_lds[lrc];
-            if (z_rows16) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zr * sl_z + cb + 16 * q, 0, 0);
-                    zq[q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-                }
-            } else {                                                      // rows on 4-byte boundaries only: the same 32 bytes as dwords
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) zq[q][w] = __builtin_amdgcn_raw_buffer_load_b32(r_z, zr * sl_z + cb + 16 * q + 4 * w, 0, 0);
-            }
-        }
+        if (p.z) sf_gate_issue(zq, r_z, zi_lds[lrc] * sl_z + cb, z_rows16);
         u32x4_t cfrag[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) cfrag[k] = *reinterpret_cast<const u32x4_t*>(cl + (SSD_TILE * lt) * PITCH + 32 * k);
@@ -526,102 +349,14 @@ __global__ __launch_bounds__(SSDW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         // ---- key tiles strictly before the query tile: factorised decay, applied to the accumulator ----
 #pragma unroll
         for (int it = 0; it < SSD_MAXT - 1; ++it) {
-            if (it < lt) {                                                // wave-uniform
-                f32x16 g;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) {                           // rows = keys 32it + 4kh + 8r4 + r, columns = queries
-                    const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(bl + (SSD_TILE * it) * PITCH + 32 * k);
-                    g = O::m32(bf, cfrag[k], g);
-                }
-                const float ad = fast_exp2(s2l - m_of(it + 1));          // alpha_l delta(lt, it)
-                uint32_t wp[8];
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 gd = *reinterpret_cast<const f32x4*>(&GD[SSD_TILE * it + 4 * kh + 8 * r4]);
-                    wp[2 * r4] = O::pack(g[4 * r4] * (gd[0] * ad), g[4 * r4 + 1] * (gd[1] * ad));
-                    wp[2 * r4 + 1] = O::pack(g[4 * r4 + 2] * (gd[2] * ad), g[4 * r4 + 3] * (gd[3] * ad));
-                }
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                    yacc = O::m32(wf, xfrag[it][ks], yacc);
-                }
-            }
+            if (it < lt)                                                  // wave-uniform; alpha_l delta(lt, it) = exp2(s2_l - m_{it+1})
+                sf_offdiag<O, NK>(yacc, bl + (SSD_TILE * it) * PITCH, cfrag, &GD[SSD_TILE * it + 4 * kh], fast_exp2(s2l - m_of(it + 1)), xfrag[it]);
         }
         // ---- the diagonal tile: dt, element-wise decay and causal mask on the accumulator of the unscaled operands ----
-        {
-            f32x16 g;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(bl + (SSD_TILE * lt) * PITCH + 32 * k);
-                g = O::m32(bf, cfrag[k], g);
-            }
-            uint32_t wp[8];
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                const f32x4 si = *reinterpret_cast<const f32x4*>(&s2[SSD_TILE * lt + 4 * kh + 8 * r4]);
-                const f32x4 di = *reinterpret_cast<const f32x4*>(&DT[SSD_TILE * lt + 4 * kh + 8 * r4]);
-                float wv[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int ik = SSD_TILE * lt + 4 * kh + 8 * r4 + r;
-                    wv[r] = (ik <= lq) ? g[4 * r4 + r] * (di[r] * fast_exp2(s2l - si[r])) : 0.0f;
-                }
-                wp[2 * r4] = O::pack(wv[0], wv[1]);
-                wp[2 * r4 + 1] = O::pack(wv[2], wv[3]);
-            }
-#pragma unroll
-            for (int it = 0; it < SSD_MAXT; ++it) {                       // (compile-time index into xfrag)
-                if (it == lt) {
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                        yacc = O::m32(wf, xfrag[it][ks], yacc);
-                    }
-                }
-            }
-        }
-        // ---- epilogue of the query tile: + D x, gate, scatter.  yacc[4 r4 + r] = Y[32lt + 4kh + 8 r4 + r][this lane's channel].
-        // One tile per wave: the lane that reads gate element (row, col) is the lane that writes the output element there. ----
-        __syncthreads();                                                  // the previous query tile's row reads are done
-        if (p.z) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4_t*>(&tile[trow * SSD_PITCH + thf * 8 + 4 * q]) = zq[q];
-        }
-        __syncthreads();
-        {
-            uint16_t* const t16 = reinterpret_cast<uint16_t*>(tile);
-#pragma unroll
-            for (int it = 0; it < SSD_MAXT; ++it) {                       // (compile-time index into xfrag)
-                if (it == lt) {
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 4 * kh + 8 * r4 + r;
-                            const int e = 4 * (r4 & 1) + r;
-                            const uint32_t xw = xfrag[it][r4 >> 1][e >> 1];
-                            const float xv = (e & 1) ? O::hi(xw) : O::lo(xw);
-                            float y = yacc[4 * r4 + r] + Dh * xv;
-                            if (p.z) y *= silu_f(O::lo((uint32_t)t16[row * (2 * SSD_PITCH) + col]));
-                            t16[row * (2 * SSD_PITCH) + col] = (uint16_t)(O::pack(y, 0.0f) & 0xffffu);
-                        }
-                }
-            }
-        }
-        __syncthreads();
-        if (lrow < L) {
-            const int orow = oi_lds[lrow];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&tile[trow * SSD_PITCH + thf * 8 + 4 * q]);
-                __builtin_amdgcn_raw_buffer_store_b128(v, r_o, orow * sl_o + cb + 16 * q, 0, 0);
-            }
-        }
+        sf_diag<O, true>(yacc, sf_scores<O, NK>(bl + (SSD_TILE * lt) * PITCH, cfrag), &s2[SSD_TILE * lt + 4 * kh], &DT[SSD_TILE * lt + 4 * kh],
+                         SSD_TILE * lt + 4 * kh, lq, s2l, xfrag[lt]);
+        // ---- epilogue of the query tile: + D x, gate, scatter, through the wave's one tile ----
+        sf_epilogue<O, true>(yacc, xfrag[lt], Dh, p.z != nullptr, zq, tile, tile, r_o, sl_o, cb, &oi_lds[lrc], lrow < L, lane);
     }
 }
 
@@ -652,27 +387,8 @@ extern "C" int dm_ssd_fwd_supported(int seqlen, int headdim, int dstate, int io_
 
 extern "C" int dm_ssd_fwd(const dm_ssd_fwd_args* args, void* stream) {
     using namespace dm;
-    if (!args) { set_error("dm_ssd_fwd: null args"); return DM_ERR_ARG; }
+    if (const int rc = ssd_fwd_check("dm_ssd_fwd", args, dm_ssd_fwd_supported, SSD_MAXL, true)) return rc;
     const dm_ssd_fwd_args& a = *args;
-    if (!a.x || !a.B || !a.C || !a.dt || !a.A || !a.out) { set_error("dm_ssd_fwd: null tensor pointer"); return DM_ERR_ARG; }
-    if (a.nseq <= 0 || a.nheads <= 0 || a.seqlen <= 0) { set_error("dm_ssd_fwd: non-positive size"); return DM_ERR_ARG; }
-    if (!dm_ssd_fwd_supported(a.seqlen, a.headdim, a.dstate, a.io_dtype)) {
-        set_error("dm_ssd_fwd: needs 16-bit I/O, headdim 64, d_state 16 / 32 / 64 / 128, seqlen <= %d (got L %d P %d N %d dtype %d)", SSD_MAXL, a.seqlen, a.headdim, a.dstate, a.io_dtype);
-        return DM_ERR_ARG;
-    }
-    if (a.nseq > 65535) { set_error("dm_ssd_fwd: nseq %d > 65535", a.nseq); return DM_ERR_ARG; }
-    if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) { set_error("dm_ssd_fwd: nseq %% batch_per_dir != 0"); return DM_ERR_ARG; }
-    if ((a.z_row_index == nullptr) != (a.out_row_index == nullptr)) { set_error("dm_ssd_fwd: both row-index tables or neither"); return DM_ERR_ARG; }
-    if (((uintptr_t)a.B & 15) || ((uintptr_t)a.C & 15) || (a.B_ss & 7) || (a.B_sl & 7) || (a.C_ss & 7) || (a.C_sl & 7)) {
-        set_error("dm_ssd_fwd: B / C rows must be 16-byte aligned"); return DM_ERR_LAYOUT;
-    }
-    if (((uintptr_t)a.x & 15) || ((uintptr_t)a.out & 15) || (a.x_ss & 7) || (a.x_sl & 7) || (a.o_ss & 7) || (a.o_sl & 7) ||
-        (a.z && a.dstate == 16 && (((uintptr_t)a.z & 15) || (a.z_ss & 7) || (a.z_sl & 7)))) {
-        set_error("dm_ssd_fwd: x / z / out rows must be 16-byte aligned (tiles move as 16-byte pieces)"); return DM_ERR_LAYOUT;
-    }
-    if (a.z && a.dstate != 16 && (((uintptr_t)a.z & 3) || (a.z_ss & 1) || (a.z_sl & 1))) {
-        set_error("dm_ssd_fwd: z rows must be 4-byte aligned at d_state %d", a.dstate); return DM_ERR_LAYOUT;
-    }
     hipStream_t st = (hipStream_t)stream;
     if (a.dstate != 16) return a.io_dtype == DM_BF16 ? ssd_fwd_wide_dispatch<bf16_t>(a, st) : ssd_fwd_wide_dispatch<f16_t>(a, st);
     dim3 grid(a.nheads * 2, a.nseq), block(WAVE);          // two 32-column halves per head

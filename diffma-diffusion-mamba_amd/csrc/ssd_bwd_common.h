@@ -63,10 +63,6 @@ __device__ __forceinline__ void wave_lds_sync() {         // make one wave's LDS
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ u32x4_t ld16(const rsrc_t& r, int byte_off) {     // one 16-byte piece of a row
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-    return (u32x4_t){v[0], v[1], v[2], v[3]};
-}
 // 8 consecutive columns (chunk) of a row of the swizzled [197][64] arrays, as an MFMA operand fragment (rows >= 196: the zero row)
 __device__ __forceinline__ u32x4_t row_frag(const uint8_t* base, int row, int chunk) {
     const int rc = row < SB_MAXL ? row : SB_MAXL;

@@ -5,10 +5,10 @@
 // prefix sums s (log2 domain: s2) and s_end the prefix sum at the chunk's last token:
 //     y_l    = [ single-chunk dual form over the keys of l's own chunk ]  +  exp(s_l) sum_n C_l[n] h[n][p]  +  D x_l
 //     h_next = exp(s_end) h  +  sum_{i in chunk} exp(s_end - s_i) dt_i B_i[n] x_i[p]                 out = y silu(z)
-// Every decay factor is a true partial decay (<= 1).  The chunk body is ssd_fwd_wide_kernel's (one workgroup per sequence and group
-// of heads, the chunk's raw B / C rows staged in LDS once, one wave per (head, 32-column half) with the chunk's X fragments resident,
-// gamma dt and alpha delta on the fp32 accumulator) for every width NK = d_state / 16 in {1, 2, 4, 8}.  The two extra products reuse
-// the fragments that body holds:
+// Every decay factor is a true partial decay (<= 1).  The chunk body is ssd_fwd_wide_kernel's: the same blocks of ssd_fwd_common.h
+// with the chunk's length in place of L (one workgroup per sequence and group of heads, the chunk's raw B / C rows staged in LDS
+// once, one wave per (head, 32-column half) with the chunk's X fragments resident, gamma dt and alpha delta on the fp32
+// accumulator) for every width NK = d_state / 16 in {1, 2, 4, 8}.  The two extra products reuse the fragments that body holds:
 //   * state, kept as h^T tiles of 32 states x 32 channels (f32x16 per tile: N / 2 registers): row 4 kh + 8 r4 + r of a tile is
 //     accumulator register 4 r4 + r, so registers 8 ks .. 8 ks + 7 rounded to the I/O dtype ARE the B-operand (K = states) of the
 //     inter-chunk product [32 queries x N] [N x 32 channels], whose A-operand is the C row read from LDS in that same state order
@@ -21,10 +21,10 @@
 //
 // One 8-wave workgroup per (sequence, 4 heads), two waves per SIMD, at every width; the chunk length follows the register budget
 // (bf16 registers; no instantiation spills; tools/kernel_regs.sh ssd_chunked):
-//     d_state  16   Q 128   247 VGPRs   43 KB LDS
-//     d_state  32   Q 128   246 VGPRs   51 KB LDS
-//     d_state  64   Q  96   248 VGPRs   58 KB LDS      (Q 128: one accumulator tile spilled)
-//     d_state 128   Q  64   256 VGPRs   65 KB LDS      (Q 128: 123 registers spilled)
+//     d_state  16   Q 128   218 VGPRs   43 KB LDS
+//     d_state  32   Q 128   226 VGPRs   51 KB LDS
+//     d_state  64   Q  96   218 VGPRs   58 KB LDS      (Q 128: one accumulator tile spilled)
+//     d_state 128   Q  64   249 VGPRs   65 KB LDS      (Q 128: 123 registers spilled)
 // The chunk body needs about 200 registers by itself and the state N / 2 more; each tile less of a chunk frees 8 of X fragments and
 // 8 in flight.  The inter-chunk term comes AFTER the diagonal tile, into an accumulator of its own: ahead of the score products it
 // kept 13 registers too many alive at d_state 128.  Per 32 tokens the intra-chunk work is (T + 1) / 2 (NK + 2) MFMAs (T = Q / 32) and
@@ -39,24 +39,21 @@
 // every chunk with the same, workgroup-uniform trip counts, so all of them meet the same barriers.  The barrier at the top of a
 // chunk keeps the restaging of B / C and the tables behind the last reads of the chunk before.
 #include <type_traits>
-#include "dm_mfma.h"
+#include "ssd_fwd_common.h"
 
 namespace dm {
 
-constexpr int SSDC_TILE = 32;
 constexpr int ssdc_t(int nk) { return nk == 8 ? 2 : (nk == 4 ? 3 : 4); }               // tiles per chunk
-constexpr int ssdc_q(int nk) { return SSDC_TILE * ssdc_t(nk); }                         // chunk length Q
+constexpr int ssdc_q(int nk) { return SSD_TILE * ssdc_t(nk); }                         // chunk length Q
 constexpr int SSDC_TABLE = 128;                              // entries per per-position table (>= Q; two positions per lane of a wave)
 constexpr int SSDC_MAXL = 1024;
-constexpr int SSDC_TPITCH = 20;                              // dwords per staged tile row (32 channels = 16 dwords, +4 pad)
 constexpr int SSDC_HEADS = 4;                                // heads per workgroup (two waves each)
 constexpr int SSDC_NTAB = 5;                                 // per head: s2 | gamma dt | dt | exp2(s2) | dt exp2(s2_end - s2)
 constexpr int SSDC_TABS = 0;
 constexpr int SSDC_IDX = SSDC_TABS + SSDC_HEADS * SSDC_NTAB * SSDC_TABLE * 4;          // z rows | out rows of the chunk (global)
 constexpr int SSDC_TILES = SSDC_IDX + 2 * SSDC_TABLE * 4;                               // one 32 x 32 staging tile per wave
-constexpr int SSDC_BC = SSDC_TILES + 2 * SSDC_HEADS * SSDC_TILE * SSDC_TPITCH * 4;   // B rows, then C rows
-constexpr int ssdc_pitch(int nk) { return 32 * nk + 16; }                               // bytes per staged B / C row (odd number of 16-byte pieces)
-constexpr int ssdc_lds_bytes(int nk, int rows) { return SSDC_BC + 2 * rows * ssdc_pitch(nk); }
+constexpr int SSDC_BC = SSDC_TILES + 2 * SSDC_HEADS * SSD_TILE * SSD_PITCH * 4;   // B rows, then C rows
+constexpr int ssdc_lds_bytes(int nk, int rows) { return SSDC_BC + 2 * rows * ssd_bc_pitch(nk); }
 static_assert(SSDC_TABLE == 2 * WAVE, "the table pass gives every lane two consecutive positions");
 static_assert(ssdc_lds_bytes(8, ssdc_q(8)) <= 160 * 1024, "LDS of a CU");
 
@@ -68,7 +65,7 @@ template <typename T, int NK>
 __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void ssd_fwd_chunked_kernel(const dm_ssd_fwd_args p) {
     using O = mfma<T>;
     constexpr int ES = (int)sizeof(T);
-    constexpr int PITCH = ssdc_pitch(NK);
+    constexpr int PITCH = ssd_bc_pitch(NK);
     constexpr int PPR = 2 * NK;                                          // 16-byte pieces of a B / C row
     constexpr int NJ = (NK + 1) / 2;                                     // state tiles of 32 states (d_state 16: half a tile)
     constexpr int KS = NK == 1 ? 1 : 2;                                  // 16-state slices per state tile
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
     const int dir = s / bpd;
     const int sb = s - dir * bpd;
     const int nchunks = (L + SSDC_Q - 1) / SSDC_Q;
-    const int rows_staged = L < SSDC_Q ? SSDC_TILE * ((L + SSDC_TILE - 1) / SSDC_TILE) : SSDC_Q;   // as the launch sizes the LDS
+    const int rows_staged = L < SSDC_Q ? SSD_TILE * ((L + SSD_TILE - 1) / SSD_TILE) : SSDC_Q;   // as the launch sizes the LDS
     const int32_t* __restrict__ zidx = p.z_row_index ? p.z_row_index + (int64_t)dir * L : nullptr;
     const int32_t* __restrict__ oidx = p.out_row_index ? p.out_row_index + (int64_t)dir * L : nullptr;
 
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
     float* const WT = S2 + 4 * SSDC_TABLE;                                   // dt_i exp2(s2_end - s2_i): key i's weight in the next state
     int* const zi_lds = reinterpret_cast<int*>(lds + SSDC_IDX);
     int* const oi_lds = zi_lds + SSDC_TABLE;
-    uint32_t* const tile = reinterpret_cast<uint32_t*>(lds + SSDC_TILES) + wave * (SSDC_TILE * SSDC_TPITCH);
+    uint32_t* const tile = reinterpret_cast<uint32_t*>(lds + SSDC_TILES) + wave * (SSD_TILE * SSD_PITCH);
     uint8_t* const Bl = lds + SSDC_BC;
     uint8_t* const Cl = Bl + rows_staged * PITCH;
 
@@ -114,9 +111,7 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
     const int cb = (h * 64 + half * 32 + thf * 16) * ES;                 // byte offset of this lane's 16 staged channels in a row
     const float Ah = p.A[h] * LOG2E, Dh = p.D ? p.D[h] : 0.0f, bias = p.dt_bias ? p.dt_bias[h] : 0.0f;
     const T* __restrict__ dtp = (const T*)p.dt + (int64_t)sb * p.dt_sb + h;
-    // the gate is a view of the in_proj output, whose rows are 2 Din + 2 N + H elements: a multiple of 8 with the factory models' 16 or
-    // 24 heads, not with the two heads of a d_model 64 mixer
-    const bool z_rows16 = (((uintptr_t)p.z & 15) | (uintptr_t)(p.z_ss & 7) | (uintptr_t)(p.z_sl & 7)) == 0;
+    const bool z_rows16 = sf_gate_rows16(p.z, p.z_ss, p.z_sl);
     // fragments of the score product G^T = B_it C_lt^T: lane (row = col, kh) holds states 16k + 8kh .. +7 of slice k
     const uint8_t* const bl = Bl + col * PITCH + 16 * kh;
     const uint8_t* const cl = Cl + col * PITCH + 16 * kh;
@@ -136,20 +131,17 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
     for (int c = 0; c < nchunks; ++c) {
         const int base = c * SSDC_Q;                                     // global index of the chunk's first token
         const int Lc = min(SSDC_Q, L - base);                            // tokens of this chunk (the last one may be ragged)
-        const int nt_c = (Lc + SSDC_TILE - 1) / SSDC_TILE;
-        const int rows = SSDC_TILE * nt_c;
+        const int nt_c = (Lc + SSD_TILE - 1) / SSD_TILE;
+        const int rows = SSD_TILE * nt_c;
 
-        // ---- X of this wave's (head, half) goes out first --------------------------------------------------------------------
+        // ---- X of this wave's (head, half) goes out first (kernel text, as the staging below: ssd_fwd_common.h says why) ---------
         u32x4_t xq[SSDC_T][2];
 #pragma unroll
         for (int it = 0; it < SSDC_T; ++it) {
-            const int i = SSDC_TILE * it + trow;
+            const int i = SSD_TILE * it + trow;
             const int ic = base + (i < Lc ? i : Lc - 1);                  // rows past the end: clamped here, zeroed below
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_x, ic * sl_x + cb + 16 * q, 0, 0);
-                xq[it][q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-            }
+            for (int q = 0; q < 2; ++q) xq[it][q] = ld16(r_x, ic * sl_x + cb + 16 * q);
         }
         __syncthreads();                                                  // every wave is done with the rows and tables of the chunk before
         // ---- the live waves' share of the chunk's B / C rows ------------------------------------------------------------------
@@ -163,10 +155,8 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
                     if (q < npieces) {
                         const int r = q / PPR, pc = q - r * PPR;
                         const int rc = base + (r < Lc ? r : Lc - 1);
-                        const auto b = __builtin_amdgcn_raw_buffer_load_b128(r_B, rc * sl_B + 16 * pc, 0, 0);
-                        const auto cc = __builtin_amdgcn_raw_buffer_load_b128(r_C, rc * sl_C + 16 * pc, 0, 0);
-                        vb[u] = (u32x4_t){b[0], b[1], b[2], b[3]};
-                        vc[u] = (u32x4_t){cc[0], cc[1], cc[2], cc[3]};
+                        vb[u] = ld16(r_B, rc * sl_B + 16 * pc);
+                        vc[u] = ld16(r_C, rc * sl_C + 16 * pc);
                     }
                 }
 #pragma unroll
@@ -225,126 +215,36 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
         }
         __syncthreads();
         const float* const s2 = S2;
-        auto m_of = [&](int t) -> float { return t == 0 ? 0.0f : s2[SSDC_TILE * t - 1]; };   // log-decay just before tile t of the chunk
+        auto m_of = [&](int t) -> float { return t == 0 ? 0.0f : s2[SSD_TILE * t - 1]; };   // log-decay just before tile t of the chunk
 
-        // ---- X as B-fragments, keys in accumulator order: slot e of (it, ks) is chunk key 32it + 4kh + 8(2ks + e/4) + e%4 ------
-        u32x4_t xfrag[SSDC_T][2];
-        {
-            const uint16_t* const t16 = reinterpret_cast<const uint16_t*>(tile);
-#pragma unroll
-            for (int it = 0; it < SSDC_T; ++it) {
-                const bool row_live = SSDC_TILE * it + trow < Lc;
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    *reinterpret_cast<u32x4_t*>(&tile[trow * SSDC_TPITCH + thf * 8 + 4 * q]) = row_live ? xq[it][q] : (u32x4_t){0u, 0u, 0u, 0u};
-                __syncthreads();
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    uint32_t w4[4];
-#pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) {
-                        const int k0 = 4 * kh + 8 * (2 * ks + (e2 >> 1)) + 2 * (e2 & 1);
-                        const uint32_t lo = t16[k0 * (2 * SSDC_TPITCH) + col], hi = t16[(k0 + 1) * (2 * SSDC_TPITCH) + col];
-                        w4[e2] = lo | (hi << 16);
-                    }
-                    xfrag[it][ks] = (u32x4_t){w4[0], w4[1], w4[2], w4[3]};
-                }
-                __syncthreads();
-            }
-        }
+        u32x4_t xfrag[SSDC_T][2];                                        // X as B-fragments, chunk keys in accumulator order
+        sf_x_frags(xfrag, xq, tile, Lc, lane);
 
 #pragma unroll
         for (int lt = 0; lt < SSDC_T; ++lt) {                            // (fully unrolled: every fragment index is a compile-time constant)
             if (lt >= nt_c) break;
-            const int lq = SSDC_TILE * lt + col;                         // this lane's query in the score tile (a column of G^T), chunk-local
+            const int lq = SSD_TILE * lt + col;                         // this lane's query in the score tile (a column of G^T), chunk-local
             const int lqc = lq < Lc ? lq : Lc - 1;
             const float s2l = s2[lqc];
             u32x4_t zq[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};            // the gate tile of this query tile, in flight under the products
-            const int lrow = SSDC_TILE * lt + trow;
+            const int lrow = SSD_TILE * lt + trow;
             const int lrc = lrow < Lc ? lrow : Lc - 1;
-            if (p.z) {
-                const int zr = zi_lds[lrc];
-                if (z_rows16) {
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const auto v = __builtin_amdgcn_raw_buffer_load_b128(r_z, zr * sl_z + cb + 16 * q, 0, 0);
-                        zq[q] = (u32x4_t){v[0], v[1], v[2], v[3]};
-                    }
-                } else {                                                  // rows on 4-byte boundaries only: the same 32 bytes as dwords
-#pragma unroll
-                    for (int q = 0; q < 2; ++q)
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) zq[q][w] = __builtin_amdgcn_raw_buffer_load_b32(r_z, zr * sl_z + cb + 16 * q + 4 * w, 0, 0);
-                }
-            }
+            if (p.z) sf_gate_issue(zq, r_z, zi_lds[lrc] * sl_z + cb, z_rows16);
             f32x16 yacc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) yacc[r] = 0.0f;
             u32x4_t cfrag[NK];
 #pragma unroll
-            for (int k = 0; k < NK; ++k) cfrag[k] = *reinterpret_cast<const u32x4_t*>(cl + (SSDC_TILE * lt) * PITCH + 32 * k);
+            for (int k = 0; k < NK; ++k) cfrag[k] = *reinterpret_cast<const u32x4_t*>(cl + (SSD_TILE * lt) * PITCH + 32 * k);
             // ---- key tiles of the chunk strictly before the query tile: factorised decay, applied to the accumulator ----
 #pragma unroll
             for (int it = 0; it < SSDC_T - 1; ++it) {
-                if (it < lt) {                                            // wave-uniform
-                    f32x16 g;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < NK; ++k) {                       // rows = keys 32it + 4kh + 8r4 + r, columns = queries
-                        const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(bl + (SSDC_TILE * it) * PITCH + 32 * k);
-                        g = O::m32(bf, cfrag[k], g);
-                    }
-                    const float ad = fast_exp2(s2l - m_of(it + 1));      // alpha_l delta(lt, it)
-                    uint32_t wp[8];
-#pragma unroll
-                    for (int r4 = 0; r4 < 4; ++r4) {
-                        const f32x4 gd = *reinterpret_cast<const f32x4*>(&GD[SSDC_TILE * it + 4 * kh + 8 * r4]);
-                        wp[2 * r4] = O::pack(g[4 * r4] * (gd[0] * ad), g[4 * r4 + 1] * (gd[1] * ad));
-                        wp[2 * r4 + 1] = O::pack(g[4 * r4 + 2] * (gd[2] * ad), g[4 * r4 + 3] * (gd[3] * ad));
-                    }
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                        yacc = O::m32(wf, xfrag[it][ks], yacc);
-                    }
-                }
+                if (it < lt)                                              // wave-uniform; alpha_l delta(lt, it) = exp2(s2_l - m_{it+1})
+                    sf_offdiag<O, NK>(yacc, bl + (SSD_TILE * it) * PITCH, cfrag, &GD[SSD_TILE * it + 4 * kh], fast_exp2(s2l - m_of(it + 1)), xfrag[it]);
             }
             // ---- the diagonal tile: dt, element-wise decay and causal mask on the accumulator of the unscaled operands ----
-            {
-                f32x16 g;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) g[r] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < NK; ++k) {
-                    const u32x4_t bf = *reinterpret_cast<const u32x4_t*>(bl + (SSDC_TILE * lt) * PITCH + 32 * k);
-                    g = O::m32(bf, cfrag[k], g);
-                }
-                uint32_t wp[8];
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 si = *reinterpret_cast<const f32x4*>(&s2[SSDC_TILE * lt + 4 * kh + 8 * r4]);
-                    const f32x4 di = *reinterpret_cast<const f32x4*>(&DT[SSDC_TILE * lt + 4 * kh + 8 * r4]);
-                    float wv[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ik = SSDC_TILE * lt + 4 * kh + 8 * r4 + r;
-                        wv[r] = (ik <= lq) ? g[4 * r4 + r] * (di[r] * fast_exp2(s2l - si[r])) : 0.0f;
-                    }
-                    wp[2 * r4] = O::pack(wv[0], wv[1]);
-                    wp[2 * r4 + 1] = O::pack(wv[2], wv[3]);
-                }
-#pragma unroll
-                for (int it = 0; it < SSDC_T; ++it) {                     // (compile-time index into xfrag)
-                    if (it == lt) {
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks) {
-                            const u32x4_t wf = {wp[4 * ks], wp[4 * ks + 1], wp[4 * ks + 2], wp[4 * ks + 3]};
-                            yacc = O::m32(wf, xfrag[it][ks], yacc);
-                        }
-                    }
-                }
-            }
+            sf_diag<O, true>(yacc, sf_scores<O, NK>(bl + (SSD_TILE * lt) * PITCH, cfrag), &s2[SSD_TILE * lt + 4 * kh], &DT[SSD_TILE * lt + 4 * kh],
+                             SSD_TILE * lt + 4 * kh, lq, s2l, xfrag[lt]);
             // ---- inter-chunk term: C_l (state order of the h^T tiles) times the carried state rounded to the I/O dtype, then
             //      exp2(s2_l) per accumulator row on the fp32 result ----
             if (c > 0) {                                                  // wave-uniform
@@ -355,7 +255,7 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
                 for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
-                        const uint8_t* const cp = cs + (SSDC_TILE * lt) * PITCH + (32 * j + 16 * ks) * 2;
+                        const uint8_t* const cp = cs + (SSD_TILE * lt) * PITCH + (32 * j + 16 * ks) * 2;
                         const ssdc_u32x2 c0 = *reinterpret_cast<const ssdc_u32x2*>(cp), c1 = *reinterpret_cast<const ssdc_u32x2*>(cp + 16);
                         const u32x4_t cf = {c0.x, c0.y, c1.x, c1.y};
                         u32x4_t hb;
@@ -365,48 +265,13 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
                     }
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    const f32x4 ex = *reinterpret_cast<const f32x4*>(&EX[SSDC_TILE * lt + 4 * kh + 8 * r4]);
+                    const f32x4 ex = *reinterpret_cast<const f32x4*>(&EX[SSD_TILE * lt + 4 * kh + 8 * r4]);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) yacc[4 * r4 + r] += yi[4 * r4 + r] * ex[r];
                 }
             }
-            // ---- epilogue of the query tile: + D x, gate, scatter.  yacc[4 r4 + r] = Y[base + 32lt + 4kh + 8 r4 + r][this lane's channel].
-            // One tile per wave: the lane that reads gate element (row, col) is the lane that writes the output element there. ----
-            __syncthreads();                                              // the previous query tile's row reads are done
-            if (p.z) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) *reinterpret_cast<u32x4_t*>(&tile[trow * SSDC_TPITCH + thf * 8 + 4 * q]) = zq[q];
-            }
-            __syncthreads();
-            {
-                uint16_t* const t16 = reinterpret_cast<uint16_t*>(tile);
-#pragma unroll
-                for (int it = 0; it < SSDC_T; ++it) {                     // (compile-time index into xfrag)
-                    if (it == lt) {
-#pragma unroll
-                        for (int r4 = 0; r4 < 4; ++r4)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const int row = 4 * kh + 8 * r4 + r;
-                                const int e = 4 * (r4 & 1) + r;
-                                const uint32_t xw = xfrag[it][r4 >> 1][e >> 1];
-                                const float xv = (e & 1) ? O::hi(xw) : O::lo(xw);
-                                float y = yacc[4 * r4 + r] + Dh * xv;
-                                if (p.z) y *= silu_f(O::lo((uint32_t)t16[row * (2 * SSDC_TPITCH) + col]));
-                                t16[row * (2 * SSDC_TPITCH) + col] = (uint16_t)(O::pack(y, 0.0f) & 0xffffu);
-                            }
-                    }
-                }
-            }
-            __syncthreads();
-            if (lrow < Lc) {
-                const int orow = oi_lds[lrow];                            // (global row: the table was built from entries base + local)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(&tile[trow * SSDC_TPITCH + thf * 8 + 4 * q]);
-                    __builtin_amdgcn_raw_buffer_store_b128(v, r_o, orow * sl_o + cb + 16 * q, 0, 0);
-                }
-            }
+            // ---- epilogue of the query tile: + D x, gate, scatter through the chunk's table (global rows: built from entries base + local) ----
+            sf_epilogue<O, true>(yacc, xfrag[lt], Dh, p.z != nullptr, zq, tile, tile, r_o, sl_o, cb, &oi_lds[lrc], lrow < Lc, lane);
         }
 
         // ---- the state after this chunk (a chunk that has a successor is full): h = exp2(s2_end) h + (B^T)(w .* X) -------------
@@ -420,14 +285,14 @@ __global__ __launch_bounds__(2 * WAVE * SSDC_HEADS) __attribute__((amdgpu_waves_
             for (int it = 0; it < SSDC_T; ++it)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(&WT[SSDC_TILE * it + 4 * kh + 16 * ks]);
-                    const f32x4 w1 = *reinterpret_cast<const f32x4*>(&WT[SSDC_TILE * it + 4 * kh + 16 * ks + 8]);
+                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(&WT[SSD_TILE * it + 4 * kh + 16 * ks]);
+                    const f32x4 w1 = *reinterpret_cast<const f32x4*>(&WT[SSD_TILE * it + 4 * kh + 16 * ks + 8]);
                     const u32x4_t xf = xfrag[it][ks];
                     const u32x4_t xw = {O::pack(O::lo(xf[0]) * w0[0], O::hi(xf[0]) * w0[1]), O::pack(O::lo(xf[1]) * w0[2], O::hi(xf[1]) * w0[3]),
                                         O::pack(O::lo(xf[2]) * w1[0], O::hi(xf[2]) * w1[1]), O::pack(O::lo(xf[3]) * w1[2], O::hi(xf[3]) * w1[3])};
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
-                        const uint8_t* const bp = bt + (SSDC_TILE * it + 16 * ks) * PITCH + 64 * j;
+                        const uint8_t* const bp = bt + (SSD_TILE * it + 16 * ks) * PITCH + 64 * j;
                         const ssdc_v4s a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ssdc_tr_ptr)bp);
                         const ssdc_v4s a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ssdc_tr_ptr)(bp + 8 * PITCH));
                         const ssdc_u32x2 v0 = __builtin_bit_cast(ssdc_u32x2, a0), v1 = __builtin_bit_cast(ssdc_u32x2, a1);
@@ -444,7 +309,7 @@ template <typename T, int NK>
 static int ssd_fwd_chunked_launch(const dm_ssd_fwd_args& a, hipStream_t st) {
     constexpr int Q = ssdc_q(NK);
     if (const int rc = reserve_dynamic_lds<&ssd_fwd_chunked_kernel<T, NK>>("dm_ssd_fwd_chunked", ssdc_lds_bytes(NK, Q))) return rc;
-    const int rows = a.seqlen < Q ? SSDC_TILE * ((a.seqlen + SSDC_TILE - 1) / SSDC_TILE) : Q;
+    const int rows = a.seqlen < Q ? SSD_TILE * ((a.seqlen + SSD_TILE - 1) / SSD_TILE) : Q;
     dim3 grid((a.nheads + SSDC_HEADS - 1) / SSDC_HEADS, a.nseq), block(2 * WAVE * SSDC_HEADS);
     hipLaunchKernelGGL((ssd_fwd_chunked_kernel<T, NK>), grid, block, ssdc_lds_bytes(NK, rows), st, a);
     return launch_status("dm_ssd_fwd_chunked");
@@ -473,26 +338,8 @@ extern "C" int dm_ssd_fwd_chunked_supported(int seqlen, int headdim, int dstate,
 extern "C" int dm_ssd_fwd_chunked(const dm_ssd_fwd_args* args, void* stream) {
     using namespace dm;
     static_assert(SSDC_MAXL == DM_SSD_FWD_CHUNKED_MAXL, "the header states the cap");
-    if (!args) { set_error("dm_ssd_fwd_chunked: null args"); return DM_ERR_ARG; }
+    if (const int rc = ssd_fwd_check("dm_ssd_fwd_chunked", args, dm_ssd_fwd_chunked_supported, SSDC_MAXL, false)) return rc;
     const dm_ssd_fwd_args& a = *args;
-    if (!a.x || !a.B || !a.C || !a.dt || !a.A || !a.out) { set_error("dm_ssd_fwd_chunked: null tensor pointer"); return DM_ERR_ARG; }
-    if (a.nseq <= 0 || a.nheads <= 0 || a.seqlen <= 0) { set_error("dm_ssd_fwd_chunked: non-positive size"); return DM_ERR_ARG; }
-    if (!dm_ssd_fwd_chunked_supported(a.seqlen, a.headdim, a.dstate, a.io_dtype)) {
-        set_error("dm_ssd_fwd_chunked: needs 16-bit I/O, headdim 64, d_state 16 / 32 / 64 / 128, seqlen <= %d (got L %d P %d N %d dtype %d)", SSDC_MAXL, a.seqlen, a.headdim, a.dstate, a.io_dtype);
-        return DM_ERR_ARG;
-    }
-    if (a.nseq > 65535) { set_error("dm_ssd_fwd_chunked: nseq %d > 65535", a.nseq); return DM_ERR_ARG; }
-    if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) { set_error("dm_ssd_fwd_chunked: nseq %% batch_per_dir != 0"); return DM_ERR_ARG; }
-    if ((a.z_row_index == nullptr) != (a.out_row_index == nullptr)) { set_error("dm_ssd_fwd_chunked: both row-index tables or neither"); return DM_ERR_ARG; }
-    if (((uintptr_t)a.B & 15) || ((uintptr_t)a.C & 15) || (a.B_ss & 7) || (a.B_sl & 7) || (a.C_ss & 7) || (a.C_sl & 7)) {
-        set_error("dm_ssd_fwd_chunked: B / C rows must be 16-byte aligned"); return DM_ERR_LAYOUT;
-    }
-    if (((uintptr_t)a.x & 15) || ((uintptr_t)a.out & 15) || (a.x_ss & 7) || (a.x_sl & 7) || (a.o_ss & 7) || (a.o_sl & 7)) {
-        set_error("dm_ssd_fwd_chunked: x / out rows must be 16-byte aligned (tiles move as 16-byte pieces)"); return DM_ERR_LAYOUT;
-    }
-    if (a.z && (((uintptr_t)a.z & 3) || (a.z_ss & 1) || (a.z_sl & 1))) {
-        set_error("dm_ssd_fwd_chunked: z rows must be 4-byte aligned"); return DM_ERR_LAYOUT;
-    }
     hipStream_t st = (hipStream_t)stream;
     return a.io_dtype == DM_BF16 ? ssd_fwd_chunked_dispatch<bf16_t>(a, st) : ssd_fwd_chunked_dispatch<f16_t>(a, st);
 }

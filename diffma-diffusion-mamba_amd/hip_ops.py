@@ -1281,11 +1281,19 @@ SSD_MFMA = os.environ.get("DIFFMA_SSD_MFMA", "1") == "1"
 # three launch sizes.  A width the C ABI serves but this tuple leaves out stays reachable through ssd_fwd() itself.  At the wide
 # states (32, 64, 128) no-grad calls (sampling, EMA evaluation) take it; training takes the A-shared scan pair unless
 # SSD_MFMA_BWD_WIDE (below) is on.  Same shape as above, dm_ssd_fwd vs scan in us at nseq 24 / 192 / 768 (profiles/ssd_fwd_wide.json, one MI355X, one session):
-#     d_state  32    32 vs 121    112 vs  281    402 vs  874      191 VGPRs,  69 KB LDS   } one 8-wave workgroup per (sequence, 4 heads),
-#     d_state  64    34 vs 122    123 vs  335    449 vs 1136      208 VGPRs,  97 KB LDS   } raw B / C rows staged in LDS: one workgroup
-#     d_state 128    38 vs 160    137 vs  872    500 vs 3264      228 VGPRs, 153 KB LDS   } per CU, 2 waves per SIMD
+#     d_state  32    32 vs 121    112 vs  281    402 vs  874      200 VGPRs,  69 KB LDS   } one 8-wave workgroup per (sequence, 4 heads),
+#     d_state  64    34 vs 122    123 vs  335    449 vs 1136      214 VGPRs,  97 KB LDS   } raw B / C rows staged in LDS: one workgroup
+#     d_state 128    38 vs 160    137 vs  872    500 vs 3264      224 VGPRs, 153 KB LDS   } per CU, 2 waves per SIMD
 # (d_state 16 in that session: 26 vs 65, 95 vs 148, 408 vs 432; its forward is within 2 % of the build before the wide kernel.)
 SSD_FWD_WIDTHS = (16, 32, 64, 128)
+
+
+def _ssd_rows_ok(views, gate, gate_unit_bytes):
+    """The rows of every view start on 16-byte boundaries and those of the gate on gate_unit_bytes (16-bit elements, dense rows)."""
+    for v, unit in [(v, 16) for v in views] + [(gate, gate_unit_bytes)]:
+        if v is not None and (v.data_ptr() % unit or v.stride(-1) != 1 or any(st % (unit // 2) for st in v.stride()[:-1])):
+            return False
+    return True
 
 
 def ssd_fwd_supported(x, L, headdim, dstate, views=(), gate=None):
@@ -1295,13 +1303,8 @@ def ssd_fwd_supported(x, L, headdim, dstate, views=(), gate=None):
         return False
     if int(dstate) not in SSD_FWD_WIDTHS:
         return False
-    for v in views:
-        if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
-            return False
-    if gate is not None:
-        unit, per = (16, 8) if int(dstate) == 16 else (4, 2)
-        if gate.data_ptr() % unit or gate.stride(-1) != 1 or any(st % per for st in gate.stride()[:-1]):
-            return False
+    if not _ssd_rows_ok(views, gate, 16 if int(dstate) == 16 else 4):
+        return False
     return bool(_lib.load().dm_ssd_fwd_supported(int(L), int(headdim), int(dstate), dtype_code(x)))
 
 
@@ -1350,12 +1353,12 @@ SSD_CHUNKED = os.environ.get("DIFFMA_SSD_CHUNKED", "1") == "1"
 # and both lengths; a width left out stays reachable through ssd_fwd_chunked().  All four qualify (worst 1.42 x: d_state 16, L 1024,
 # nseq 192).  DiffMa-XL/2 mixer shape (16 heads x 64, bf16, three directions), ssd_fwd_chunked() vs the scan in us at nseq 3 / 24 / 192,
 # L = 256 | L = 1024 (profiles/ssd_fwd_chunked.json, one MI355X, one session, alternating windows, spread <= 0.4 %):
-#     d_state  16      31 vs    75     33 vs    91    109 vs   179  |    116 vs   256    128 vs   291    449 vs   636      Q 128, 247 VGPRs, 43 KB LDS
-#     d_state  32      32 vs   127     34 vs   146    110 vs   327  |    121 vs   467    132 vs   517    460 vs  1223      Q 128, 246 VGPRs, 51 KB LDS
-#     d_state  64      35 vs   108     37 vs   145    121 vs   386  |    134 vs   389    145 vs   500    499 vs  1486      Q  96, 248 VGPRs, 58 KB LDS
-#     d_state 128      39 vs   109     41 vs   188    135 vs  1102  |    155 vs   390    165 vs   668    555 vs  4272      Q  64, 256 VGPRs, 65 KB LDS
+#     d_state  16      31 vs    75     33 vs    91    109 vs   179  |    116 vs   256    128 vs   291    449 vs   636      Q 128, 218 VGPRs, 43 KB LDS
+#     d_state  32      32 vs   127     34 vs   146    110 vs   327  |    121 vs   467    132 vs   517    460 vs  1223      Q 128, 226 VGPRs, 51 KB LDS
+#     d_state  64      35 vs   108     37 vs   145    121 vs   386  |    134 vs   389    145 vs   500    499 vs  1486      Q  96, 218 VGPRs, 58 KB LDS
+#     d_state 128      39 vs   109     41 vs   188    135 vs  1102  |    155 vs   390    165 vs   668    555 vs  4272      Q  64, 249 VGPRs, 65 KB LDS
 # One 8-wave workgroup per (sequence, 4 heads), two waves per SIMD, at every width; no instantiation spills, no scratch (bf16 figures;
-# fp16 needs 4 - 21 registers fewer; tools/kernel_regs.sh ssd_chunked).
+# fp16 needs 22 - 62 registers fewer; tools/kernel_regs.sh ssd_chunked).
 SSD_FWD_CHUNKED_WIDTHS = (16, 32, 64, 128)
 
 
@@ -1365,10 +1368,7 @@ def ssd_fwd_chunked_supported(x, L, headdim, dstate, views=(), gate=None):
         return False
     if int(dstate) not in SSD_FWD_CHUNKED_WIDTHS:
         return False
-    for v in views:
-        if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
-            return False
-    if gate is not None and (gate.data_ptr() % 4 or gate.stride(-1) != 1 or any(st % 2 for st in gate.stride()[:-1])):
+    if not _ssd_rows_ok(views, gate, 4):
         return False
     return bool(_lib.load().dm_ssd_fwd_chunked_supported(int(L), int(headdim), int(dstate), dtype_code(x)))
 
@@ -1406,13 +1406,8 @@ def ssd_bwd_supported(x, L, headdim, dstate, views=(), gate=None):
     wide = int(dstate) != 16
     if wide and not (SSD_MFMA_BWD_WIDE and int(dstate) in SSD_BWD_WIDE_WIDTHS):
         return False
-    for v in views:
-        if v is not None and (v.data_ptr() % 16 or v.stride(-1) != 1 or any(st % 8 for st in v.stride()[:-1])):
-            return False
-    if gate is not None:
-        unit, per = (4, 2) if wide else (16, 8)
-        if gate.data_ptr() % unit or gate.stride(-1) != 1 or any(st % per for st in gate.stride()[:-1]):
-            return False
+    if not _ssd_rows_ok(views, gate, 4 if wide else 16):
+        return False
     lib = _lib.load()
     supported = lib.dm_ssd_bwd_wide_supported if wide else lib.dm_ssd_bwd_supported
     return bool(supported(int(L), int(headdim), int(dstate), dtype_code(x)))

@@ -16,16 +16,16 @@ keeps |out| < 4096 in the fp64 reference (asserted), well inside fp16's range.
 
 Bound.  u, T, EPS32, C32, K0f, P1, P2 as in tests/test_ssd_gpu.py's docstring and tests/test_ssd_wide_cpu.fwd_bound; chunk boundaries
 are tile boundaries, so a pair (l, i) of ONE chunk sees the same alpha, gamma, delta whether the prefix sums are chunk-local or not
-and is charged exactly as there (three roundings allowed, the kernel spends one: the score tile, ssd_chunked.hip:303-304 and :334-335).
+and is charged exactly as there (three roundings allowed, the kernel spends one: the score tile, sf_offdiag and sf_diag of ssd_fwd_common.h).
 A pair whose key lies in an EARLIER chunk (nch = chunks between them >= 1) is charged what the kernel does on that path:
-  * two 16-bit roundings: the weighted operand rnd(dt_i exp(s_end - s_i) x_ip) of the state update (:426-427) and the carried state
-    rnd(h[n][p]) where the query tile reads it (:363; once however many chunks it crossed: h travels in fp32).  |h| is at most the
+  * two 16-bit roundings: the weighted operand rnd(dt_i exp(s_end - s_i) x_ip) of the state update (`xw`) and the carried state
+    rnd(h[n][p]) where the query tile reads it (`hb`; once however many chunks it crossed: h travels in fp32).  |h| is at most the
     S-form sum_i |B_in| w_i |x_ip| (1 + u), so both are relative to Wabs |x|:   ((1 + u)^2 - 1) Wabs
     and in the subnormal range absolute: T per weighted operand, which reaches the output through |C_l| . |B_i| and the decay from the
     end of the key's chunk (Mend), and T per state element, through exp(s_l - s_start) sum_n |C_ln| once per query:
         Ta[l] = T (1 + u) sum_i Gabs[l, i] Mend[l, i],      Tb[l] = T exp(s_l - s_start(l)) sum_n |C_ln|
-  * fp32: the exponent of the pair's decay is now a sum of chunk-local prefix sums -- s_l local (EX, :214), s_end of every chunk
-    between (dec, :414), s_end - s_i of the key's chunk (WT, :215) -- each an 8-addition sum with the sign of A (10 EPS32 of its
+  * fp32: the exponent of the pair's decay is now a sum of chunk-local prefix sums -- s_l local (EX), s_end of every chunk
+    between (dec), s_end - s_i of the key's chunk (WT) -- each an 8-addition sum with the sign of A (10 EPS32 of its
     magnitude) and one more rounding for a difference; their magnitudes add up to at most 2 |s_l| + |s_i| (global), so
         C32x = C32 + 12 EPS32 |s_l|
     and the extra exp2s and products (one v_exp_f32 at 2 EPS32 and one product per link of the chain: 3 nch), the exp2 and the
@@ -49,7 +49,7 @@ import pytest
 import torch
 
 from tests.test_ssd_gpu import BF16, BIAS_H, DT_LEVEL, EPS32, F16, NAME, P, TILE, TINY, UNIT, _decay, _dual, _ratio, _silu, _softplus
-from tests.test_ssd_wide_cpu import _rows, head_params
+from tests.test_ssd_wide_cpu import _rows, head_params, unit_gate
 
 WIDTHS = [16, 32, 64, 128]
 MAXL = 1024
@@ -156,8 +156,9 @@ def chunked(q, A, D, Q, rnd=None, defect=None):
     return r(pre), pre
 
 
-def chunked_bound(q, A, D, dtype, ref_out, Q):
-    """The bound of the module docstring for one sequence (scan order)."""
+def chunked_bound(q, A, D, dtype, ref_out, Q, gate=True):
+    """The bound of the module docstring for one sequence (scan order).  gate False: the operator without a gate, as
+    tests/test_ssd_wide_cpu.fwd_bound."""
     u, T = UNIT[dtype], TINY[dtype]
     L, N = q["B"].shape
     nh = A.shape[0]
@@ -176,8 +177,8 @@ def chunked_bound(q, A, D, dtype, ref_out, Q):
     C32 = EPS32 * 12 * (sT.abs()[:, :, None] + sT.abs()[:, None, :]) + (errs[:, :, None] - errs[:, None, :]).clamp_min(0) + eps_dt.t()[:, None, :]
     Gabs = (Cm @ Bm.t())[None]
     Wabs = Gabs * Mdt
-    cz = EPS32 * (2 * z.abs() + 12)
-    silu = _silu(z).abs()
+    cz = EPS32 * (2 * z.abs() + 12) if gate else torch.zeros_like(z)
+    silu = _silu(z).abs() if gate else torch.ones_like(z)
     mm = lambda E, v: torch.einsum("hli,ihp->lhp", E, v)
     # ---- pairs of one chunk: tests/test_ssd_wide_cpu.fwd_bound ----
     m = torch.cat([torch.zeros(nh, 1, dtype=s.dtype), sT[:, TILE - 1::TILE], sT[:, -1:]], 1)
@@ -205,17 +206,20 @@ def chunked_bound(q, A, D, dtype, ref_out, Q):
 
 
 @functools.lru_cache(maxsize=None)
-def analysis(L, dtype, N, nh=4, family="randn"):
-    """(ref, tol) [S, L, nh * P] of one case in the kernel's output layout: the fp64 dual form and its bound.  Computed once per case."""
+def analysis(L, dtype, N, nh=4, family="randn", gate=True):
+    """(ref, tol) [S, L, nh * P] of one case in the kernel's output layout: the fp64 dual form and its bound.  Computed once per case.
+    gate False: the same operands without the gate, out = Y + D x."""
     c = inputs(L, dtype, N, nh, family)
     A, D, _ = head_params(nh)
     Q = chunk_len(N)
     ref, tol = [], []
     for s in range(c["S"]):
         q = seq(c, s)
+        if not gate:
+            q = {**q, "z": torch.full_like(q["z"], unit_gate())}
         out = _dual(q, A, D)
         ref.append(_rows(out, q["oi"], L))
-        tol.append(_rows(chunked_bound(q, A, D, dtype, out, Q), q["oi"], L))
+        tol.append(_rows(chunked_bound(q, A, D, dtype, out, Q, gate), q["oi"], L))
     return torch.stack(ref), torch.stack(tol)
 
 

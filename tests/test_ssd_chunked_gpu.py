@@ -23,8 +23,8 @@ LENGTH = {"Q+1": lambda Q: Q + 1, "2Q": lambda Q: 2 * Q, "2Q+33": lambda Q: 2 * 
           "1": lambda Q: 1, "33": lambda Q: 33, "Q": lambda Q: Q}
 
 
-def _launch(gpu, c, N, nh, dtype, gate_pad=0, entry="ssd_fwd_chunked"):
-    """Device buffers of the case and one launch: (framed buffer, out view, operand buffers and their copies)."""
+def _launch(gpu, c, N, nh, dtype, gate_pad=0, entry="ssd_fwd_chunked", gate=True):
+    """Device buffers of the case and one launch: (framed buffer, out view, operand buffers and their copies).  gate False: z = None."""
     from diffma_amd import hip_ops
 
     L, S, din = c["L"], c["S"], nh * P
@@ -40,20 +40,20 @@ def _launch(gpu, c, N, nh, dtype, gate_pad=0, entry="ssd_fwd_chunked"):
     view = buf[:, 2:2 + L, :din]
     view.fill_(NAN)
     A, D, bias = (t.float().to(gpu) for t in head_params(nh))
-    out = getattr(hip_ops, entry)(x, Bm, Cm, c["dt_tok"].to(gpu), z, A, D, bias, out=view, z_row_index=c["zperm"].int().to(gpu),
+    out = getattr(hip_ops, entry)(x, Bm, Cm, c["dt_tok"].to(gpu), z if gate else None, A, D, bias, out=view, z_row_index=c["zperm"].int().to(gpu),
                                   out_row_index=c["operm"].int().to(gpu), batch_per_dir=c["bpd"])
     torch.cuda.synchronize()
     assert out.data_ptr() == view.data_ptr()
     return buf, view, (xb, xb0, zb, zb0)
 
 
-def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0, family="randn"):
+def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0, family="randn", gate=True):
     """One launch of hip_ops.ssd_fwd_chunked: every element of out within the bound, the frame around out bit for bit, the operands
-    unchanged."""
+    unchanged.  gate False: the launch gets z = None and is held to the reference and the bound of the operator without a gate."""
     c = inputs(L, dtype, N, nh, family)
-    ref, tol = analysis(L, dtype, N, nh, family)
+    ref, tol = analysis(L, dtype, N, nh, family, gate)
     S, din = c["S"], nh * P
-    buf, view, (xb, xb0, zb, zb0) = _launch(gpu, c, N, nh, dtype, gate_pad)
+    buf, view, (xb, xb0, zb, zb0) = _launch(gpu, c, N, nh, dtype, gate_pad, gate=gate)
     chk = buf.clone()
     chk[:, 2:2 + L, :din] = SENT
     assert bool((chk == SENT).all()), "written outside out"
@@ -61,7 +61,7 @@ def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0, family="randn"):
     r = _ratio(view.cpu().reshape(S, L, din), ref, tol)
     worst = float(r.max())
     per_head = [round(float(r.reshape(S, L, nh, P)[:, :, h].max()), 3) for h in range(nh)]
-    print(f"worst |got - ref| / bound  out N {N} {NAME[dtype]} L {L} heads {nh} {family}: {worst:.4f}")
+    print(f"worst |got - ref| / bound  out N {N} {NAME[dtype]} L {L} heads {nh} {family}{'' if gate else ' no gate'}: {worst:.4f}")
     assert worst <= 1.0, f"out N {N} {NAME[dtype]} L {L} {family}: worst |got - ref| / bound {worst:.3f}; per head {per_head}"
 
 
@@ -106,6 +106,14 @@ def test_ssd_fwd_chunked_head_counts(gpu, nh):
 def test_ssd_fwd_chunked_gate_rows_on_4_byte_boundaries(gpu, N):
     """The gate of a two-head mixer starts its rows on 4-byte boundaries only; the chunked entry takes that at every width."""
     _run_case(gpu, 2 * chunk_len(N) + 33, BF16, N, 2, gate_pad=2)
+
+
+@pytest.mark.parametrize("N", [16, 128])
+def test_ssd_fwd_chunked_without_gate(gpu, N):
+    """dm_ssd_fwd_chunked with z = NULL, the arm no other kernel-level test reaches: d_state 16 and 128, bf16, L = Q + 1 (a full
+    chunk and one token that reads the carried state), three heads.  Reference: the fp64 dual form with out = Y + D x; bound:
+    tests.test_ssd_chunked_cpu.chunked_bound without the gate's factor and error term."""
+    _run_case(gpu, chunk_len(N) + 1, BF16, N, 3, gate=False)
 
 
 def test_ssd_fwd_chunked_is_deterministic(gpu):

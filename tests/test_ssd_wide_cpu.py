@@ -85,8 +85,20 @@ def seq(c, s, table0=False):
                 zi=zi, oi=oi)
 
 
-def fwd_bound(q, A, D, dtype, ref_out):
-    """The forward bound of test_ssd_gpu.py's docstring for one sequence (scan order), K0 = 72 + 2 (N - 16) + 2 (l + 1)."""
+@functools.lru_cache(maxsize=None)
+def unit_gate():
+    """z0 with silu(z0) = 1 (1.27846...): the fp64 functions multiply by silu(z), and with this gate that factor is the identity to
+    an ulp of fp64 -- the operator without a gate, out = Y + D x."""
+    z0 = torch.tensor(1.0, dtype=torch.float64)
+    for _ in range(60):                                                                  # Newton on z sigmoid(z) = 1
+        sg = torch.sigmoid(z0)
+        z0 = z0 - (z0 * sg - 1.0) / (sg * (1.0 + z0 * (1.0 - sg)))
+    return float(z0)
+
+
+def fwd_bound(q, A, D, dtype, ref_out, gate=True):
+    """The forward bound of test_ssd_gpu.py's docstring for one sequence (scan order), K0 = 72 + 2 (N - 16) + 2 (l + 1).  gate False:
+    the operator without a gate -- the factor silu(z) is 1 and its fp32 error term c_z is not charged."""
     u, T = UNIT[dtype], TINY[dtype]
     L, N = q["B"].shape
     nh = A.shape[0]
@@ -104,8 +116,8 @@ def fwd_bound(q, A, D, dtype, ref_out):
     errs = (A.abs() * (eps_dt * dt).cumsum(0)).t()
     C32 = EPS32 * 12 * (sT.abs()[:, :, None] + sT.abs()[:, None, :]) + (errs[:, :, None] - errs[:, None, :]).clamp_min(0) + eps_dt.t()[:, None, :]
     Wabs = (Cm @ Bm.t())[None] * Mdt
-    cz = EPS32 * (2 * z.abs() + 12)
-    silu = _silu(z).abs()
+    cz = EPS32 * (2 * z.abs() + 12) if gate else torch.zeros_like(z)
+    silu = _silu(z).abs() if gate else torch.ones_like(z)
     mm = lambda E, v: torch.einsum("hli,ihp->lhp", E, v)
     m = torch.cat([torch.zeros(nh, 1, dtype=s.dtype), sT[:, TILE - 1::TILE], sT[:, -1:]], 1)
     alpha, gamma = torch.exp(sT - m[:, tl]), torch.exp(m[:, tl + 1] - sT)
@@ -124,16 +136,19 @@ def _rows(v, oi, L):
 
 
 @functools.lru_cache(maxsize=None)
-def analysis(L, dtype, N, nh=4):
-    """(ref, tol) [S, L, nh * P] of one case in the kernel's output layout: fp64 dual form and its bound.  Computed once per case."""
+def analysis(L, dtype, N, nh=4, gate=True):
+    """(ref, tol) [S, L, nh * P] of one case in the kernel's output layout: fp64 dual form and its bound.  Computed once per case.
+    gate False: the same operands without the gate, out = Y + D x."""
     c = inputs(L, dtype, N, nh)
     A, D, _ = head_params(nh)
     ref, tol = [], []
     for s in range(c["S"]):
         q = seq(c, s)
+        if not gate:
+            q = {**q, "z": torch.full_like(q["z"], unit_gate())}
         out = _dual(q, A, D)
         ref.append(_rows(out, q["oi"], L))
-        tol.append(_rows(fwd_bound(q, A, D, dtype, out), q["oi"], L))
+        tol.append(_rows(fwd_bound(q, A, D, dtype, out, gate), q["oi"], L))
     return torch.stack(ref), torch.stack(tol)
 
 

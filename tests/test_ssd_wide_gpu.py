@@ -23,13 +23,14 @@ def _lib():
     return L
 
 
-def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0):
+def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0, gate=True):
     """One launch of hip_ops.ssd_fwd on the case (L, dtype, N, nh): every element of out within the bound, the frame around out
-    bit for bit, the operands unchanged.  gate_pad: spare columns behind every row of z (2: rows on 4-byte boundaries only)."""
+    bit for bit, the operands unchanged.  gate_pad: spare columns behind every row of z (2: rows on 4-byte boundaries only).
+    gate False: the launch gets z = None and is held to the reference and the bound of the operator without a gate."""
     from diffma_amd import hip_ops
 
     c = inputs(L, dtype, N, nh)
-    ref, tol = analysis(L, dtype, N, nh)
+    ref, tol = analysis(L, dtype, N, nh, gate)
     S, din = c["S"], nh * P
     xb = torch.full((S, L + 4, din + 2 * N + 8), NAN, dtype=dtype, device=gpu)           # NaN rows before / after, NaN columns beside
     xb[:, 2:2 + L, :din + 2 * N] = c["xBC"].to(gpu)
@@ -43,7 +44,7 @@ def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0):
     view = buf[:, 2:2 + L, :din]
     view.fill_(NAN)
     A, D, bias = (t.float().to(gpu) for t in head_params(nh))
-    out = hip_ops.ssd_fwd(x, Bm, Cm, c["dt_tok"].to(gpu), z, A, D, bias, out=view, z_row_index=c["zperm"].int().to(gpu),
+    out = hip_ops.ssd_fwd(x, Bm, Cm, c["dt_tok"].to(gpu), z if gate else None, A, D, bias, out=view, z_row_index=c["zperm"].int().to(gpu),
                           out_row_index=c["operm"].int().to(gpu), batch_per_dir=c["bpd"])
     torch.cuda.synchronize()
     chk = buf.clone()
@@ -53,7 +54,7 @@ def _run_case(gpu, L, dtype, N, nh=4, gate_pad=0):
     r = _ratio(view.cpu().reshape(S, L, din), ref, tol)
     worst = float(r.max())
     per_head = [round(float(r.reshape(S, L, nh, P)[:, :, h].max()), 3) for h in range(nh)]
-    print(f"worst |got - ref| / bound  out N {N} {NAME[dtype]} L {L} heads {nh}: {worst:.4f}")
+    print(f"worst |got - ref| / bound  out N {N} {NAME[dtype]} L {L} heads {nh}{'' if gate else ' no gate'}: {worst:.4f}")
     assert worst <= 1.0, f"out N {N} {NAME[dtype]} L {L}: worst |got - ref| / bound {worst:.3f}; per head {per_head}"
 
 
@@ -78,6 +79,14 @@ def test_ssd_fwd_wide_gate_rows_on_4_byte_boundaries(gpu, dtype):
     which the wide kernel reads as dwords.  Same bound; d_state 128, two heads, L = 65 and 33."""
     for L in (65, 33):
         _run_case(gpu, L, dtype, 128, 2, gate_pad=2)
+
+
+@pytest.mark.parametrize("N", [16, 128])
+def test_ssd_fwd_without_gate(gpu, N):
+    """dm_ssd_fwd with z = NULL, the arm no other kernel-level test reaches: d_state 16 (ssd_fwd_kernel) and 128 (the wide kernel),
+    bf16, L = 33 (two tiles, the second ragged), three heads (one surplus head in the wide workgroup).  Reference: the fp64 dual form
+    with out = Y + D x; bound: tests.test_ssd_wide_cpu.fwd_bound without the gate's factor and error term."""
+    _run_case(gpu, 33, BF16, N, 3, gate=False)
 
 
 def _logged(monkeypatch):
