@@ -22,8 +22,11 @@ static int check_scan_bwd(const dm_scan_bwd_args& a) {
         a.B_sn != 1 || a.C_sn != 1) {
         set_error("dm_selective_scan_bwd: needs token-major tensors (channel stride 1, state stride 1)"); return DM_ERR_LAYOUT;
     }
-    if (a.dim % a.ngroups != 0 || (a.ngroups > 1 && (a.dim / a.ngroups) % WAVE != 0)) {
-        set_error("dm_selective_scan_bwd: dim/ngroups must be a multiple of 64"); return DM_ERR_LAYOUT;
+    // K2 and K2c take ONE grp per workgroup (256 / SPLIT channels), stage one B/C row and write one dB/dC partial row for it; the
+    // caller then sums the rows of all workgroups into one [S, L, 2N].  With several B/C groups that is a wrong answer, not a slow one.
+    if (a.ngroups != 1) {
+        set_error("dm_selective_scan_bwd: ngroups=%d: the backward is built for one B/C group (ngroups = 1); only the forward serves groups", a.ngroups);
+        return DM_ERR_ARG;
     }
     if (a.batch_per_dir > 0 && a.nseq % a.batch_per_dir != 0) { set_error("dm_selective_scan_bwd: nseq %% batch_per_dir != 0"); return DM_ERR_ARG; }
     if ((a.flags & DM_FLAG_DELTA_ACTIVATED) && (a.z || !a.z_row_index || a.dstate != 16 || (a.flags & (DM_FLAG_A_SHARED | DM_FLAG_DELTA_SOFTPLUS)))) {

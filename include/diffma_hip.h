@@ -276,7 +276,8 @@ int dm_scan_fwd_launch_segment(int nseq, int dim, int seqlen, int dstate, int fl
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t nseq, dim, seqlen, dstate;
-    int32_t ngroups;
+    int32_t ngroups;         /* must be 1: the backward stages one B/C row and writes one dB/dC partial row per workgroup; anything else
+                                returns DM_ERR_ARG before a launch (the forward serves ngroups > 1 with dim / ngroups a multiple of 64) */
     int32_t batch_per_dir;
     int32_t io_dtype;
     int32_t bc_dtype;
